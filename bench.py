@@ -9,6 +9,14 @@ sharded across ranks (weak scaling); weights are broadcast once over RCCL and
 each step's 3D joints are gathered to rank 0 (the only collectives).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--views V]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+value and ms_per_step).  --dump-outputs DIR also writes what the last timed step returned
+(DIR/kpts_2d.npy, heatmaps_2d.npy, kpts_3d.npy; the inputs are seeded, so two builds can be
+compared output for output).  --full adds everything else after the timed region: the
+backbone's roofline line, the per-stage and triangulation lines, the config 3 / config 5 /
+detector / video / ingest side lines and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -47,12 +55,20 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--frames", type=int, default=256, help="synchronised frames per step per GPU")
     ap.add_argument("--views", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the roofline / per-kernel lines, the side lines and "
+                         "the CPU baseline (minutes); off: the headline run only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-frames", type=int, default=12,
                     help="frames of the all-threads CPU baseline sample (config 1 is 50 frames)")
     ap.add_argument("--cpu-sample-frames-1t", type=int, default=2, help="frames of the 1-thread sample")
-    ap.add_argument("--no-extra", action="store_true", help="skip the config 3 / config 5 side lines")
-    return ap.parse_args()
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the config 3 / config 5 side lines")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(n):
@@ -557,56 +573,25 @@ def detector_line(dev, est, cams_params, V, batch=None, reps=5):
     return res
 
 
-def main():
-    args = parse()
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(spawn_ranks(args.gpus))
-    world, rank, dev = setup_dist(args)
-    from mvpose import dist as mdist, hrnet, ops, synthetic as syn
-    from mvpose.estimator import BatchPoseEstimator
-    from mvpose.pipeline import MultiViewPipeline
+def dump_outputs(path, pipe, o, all_3d):
+    """What a caller of the timed path holds after its last step, as float32 / float64 .npy files
+    (the whole arrays: 0.4 MB at the default batch): rank 0's kpts_2d (T, 17, 3, V) and heatmaps_2d
+    (T, V, 17, 6) from process(), and kpts_3d (world x T, 17, 3) as gathered to rank 0."""
+    pipe.wait(o)   # heatmaps_2d was computed on the side stream
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+    arrays = {"kpts_2d": o["kpts_2d"], "heatmaps_2d": o["heatmaps_2d"], "kpts_3d": all_3d}
+    for name, t in arrays.items():
+        a = t.cpu().numpy()
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
 
+
+def full_lines(args, est, frames, cams, rank, dev):
+    """--full: everything beside the headline, after the timed region.  Every rank times its
+    backbone; rank 0 adds the per-stage, triangulation and side lines."""
+    from mvpose import ops, synthetic as syn
     B, V = args.frames, args.views
-    est = BatchPoseEstimator(hrnet.random_state_dict(0), max_frames=B * V, device=dev)
-    # the weights live once on rank 0; ship them over RCCL (xGMI) and re-derive each rank's
-    # graph copies (the only start-up collective)
-    est.backbone.sync_weights(src=0)
-    cams = syn.make_rig(V, seed=1)
-    pipe = MultiViewPipeline(syn.reference_camera_params(cams), estimator=est, device=dev)
-    g = torch.Generator(device=dev).manual_seed(1234 + rank)
-    frames = torch.randint(0, 256, (B, V, 720, 1280, 3), dtype=torch.uint8, device=dev, generator=g)
-    out = {}
-
-    def step():
-        o = pipe.process(frames, out, overlap_moments=True)  # moments beside the next backbone
-        mdist.gather_frames(o["kpts_3d"], world * B)   # per-step 3D joints to rank 0 (204 B/frame)
-        return o
-
-    for _ in range(args.warmup):
-        step()
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
-    rank_ms = [1e3 * elapsed / args.steps]
-    rccl_world = 1
-    if world > 1:
-        # every rank's own step time to rank 0 (shows a lagging rank), then the max = the job's time
-        rccl_world = torch.distributed.get_world_size()
-        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        parts = [torch.empty_like(t) for _ in range(rccl_world)]
-        torch.distributed.all_gather(parts, t)
-        rank_ms = [1e3 * float(p.item()) / args.steps for p in parts]
-        elapsed = max(float(p.item()) for p in parts)
-
     # ---- per-kernel timing with HIP events on the launch stream (not part of the timed region)
     s = torch.cuda.current_stream(dev)
     crops = est.crops[: 2 * B * V]
@@ -622,9 +607,14 @@ def main():
     bb_tflops = flops / (bb_ms * 1e-3) / 1e12
     extra = {}
     if rank == 0:
-        traffic_all, _ = committed_traffic()
-        extra["stages"] = stage_lines(est, frames.reshape(B * V, 720, 1280, 3), traffic_all)
-        del frames
+        traffic, traffic_src = committed_traffic()
+        extra["roofline"] = {"bound": "mfma", "kernel": "HRNet-W32 conv graph (one graph forward = one launch)",
+                             "achieved": bb_tflops, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": bb_tflops / BF16_PEAK_TFLOPS,
+                             "traffic": traffic.get("backbone", {}).get("hbm_bytes_per_launch"),
+                             "traffic_source": traffic_src, "flops_per_launch": flops, "avg_launch_ms": bb_ms,
+                             "breakdown_source": BREAKDOWN_FILE}
+        extra["stages"] = stage_lines(est, frames.reshape(B * V, 720, 1280, 3), traffic)
         torch.cuda.empty_cache()
         if V == 2:
             tri = tri_line(ops, syn, dev, s, V, ops.TRI_REFERENCE, tolerance=True)
@@ -650,9 +640,67 @@ def main():
             extra["host_ingest"] = ingest_line(est, V)
             extra["video_decode"] = video_decode_line()
             extra["detector"] = detector_line(dev, est, syn.reference_camera_params(cams), V)
+    return extra
+
+
+def main():
+    args = parse()
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        sys.exit(spawn_ranks(args.gpus))
+    world, rank, dev = setup_dist(args)
+    from mvpose import dist as mdist, hrnet, synthetic as syn
+    from mvpose.estimator import BatchPoseEstimator
+    from mvpose.pipeline import MultiViewPipeline
+
+    B, V = args.frames, args.views
+    est = BatchPoseEstimator(hrnet.random_state_dict(0), max_frames=B * V, device=dev)
+    # the weights live once on rank 0; ship them over RCCL (xGMI) and re-derive each rank's
+    # graph copies (the only start-up collective)
+    est.backbone.sync_weights(src=0)
+    cams = syn.make_rig(V, seed=1)
+    pipe = MultiViewPipeline(syn.reference_camera_params(cams), estimator=est, device=dev)
+    g = torch.Generator(device=dev).manual_seed(1234 + rank)
+    frames = torch.randint(0, 256, (B, V, 720, 1280, 3), dtype=torch.uint8, device=dev, generator=g)
+    out = {}
+
+    def step():
+        o = pipe.process(frames, out, overlap_moments=True)  # moments beside the next backbone
+        all_3d = mdist.gather_frames(o["kpts_3d"], world * B)   # per-step 3D joints to rank 0 (204 B/frame)
+        return o, all_3d
+
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        last, last_3d = step()
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    rank_ms = [1e3 * elapsed / args.steps]
+    rccl_world = 1
+    if world > 1:
+        # every rank's own step time to rank 0 (shows a lagging rank), then the max = the job's time
+        rccl_world = torch.distributed.get_world_size()
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        parts = [torch.empty_like(t) for _ in range(rccl_world)]
+        torch.distributed.all_gather(parts, t)
+        rank_ms = [1e3 * float(p.item()) / args.steps for p in parts]
+        elapsed = max(float(p.item()) for p in parts)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe, last, last_3d)
+
+    extra = {}
+    if args.full:
+        extra = full_lines(args, est, frames, cams, rank, dev)
 
     if rank == 0:
-        traffic, traffic_src = committed_traffic()
         total_frames = world * B * args.steps
         res = {
             "metric": METRIC,
@@ -672,15 +720,9 @@ def main():
                        "crops_per_step_per_gpu": 2 * B * V, "parallelism": f"dp{world} (frame-sharded)"},
             "rccl_world": rccl_world,
             "rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms},
-            "roofline": {"bound": "mfma", "kernel": "HRNet-W32 conv graph (one graph forward = one launch)",
-                         "achieved": bb_tflops, "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": bb_tflops / BF16_PEAK_TFLOPS,
-                         "traffic": traffic.get("backbone", {}).get("hbm_bytes_per_launch"),
-                         "traffic_source": traffic_src, "flops_per_launch": flops, "avg_launch_ms": bb_ms,
-                         "breakdown_source": BREAKDOWN_FILE},
         }
         res.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.cpu_sample_frames, args.cpu_sample_frames_1t, V)
         print(json.dumps(res))
     if world > 1:
