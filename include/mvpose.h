@@ -98,6 +98,41 @@ int mvp_triangulate(const float* kpts_dev, int64_t n_points, int V, const double
 int mvp_triangulate_fallback_total(void* stream, unsigned long long* out_total_host);
 
 /* ---------------------------------------------------------------------------
+ * mvp_triangulate_robust — N-view triangulation with per-point outlier-view rejection, an
+ * inlier mask and a reprojection-error read-out.  No reference counterpart (the reference
+ * triangulates from two cameras only).
+ *
+ * kpts_dev, cams_dev, cam_idx_host / n_cam_idx as for mvp_triangulate in MVP_TRI_ALL_VIEWS mode:
+ * view i reads column cam_idx[i] and the parameters of camera cam_idx[i]; fp64, OpenCV 4.9
+ * undistortion restated, f32 undistorted points.
+ *   Valid view: x and y finite, conf not NaN and conf >= min_conf, undistorted point finite.
+ *   Reprojection error of view i against a homogeneous X: q = P_i·X in fp64; if q[2]·X[3] > 0
+ *     (in front of the camera) hypot(q0/q2 - ux_i, q1/q2 - uy_i) in undistorted pixels against
+ *     the f32 undistorted point, else +inf.
+ *   Step A: fewer than 2 valid views -> xyz NaN, mask 0, errors NaN.  Otherwise the DLT over all
+ *     valid views, its float32 xyz as mvp_triangulate writes it, and each valid view's error
+ *     against (x, y, z, 1); if every one is <= inlier_px the point is done, mask = valid views.
+ *   Step B (other points): for each pair (a, b), a < b, of valid views in lexicographic order,
+ *     the fp64 null vector of the 4x4 two-view DLT is a hypothesis; its inliers are the valid
+ *     views with error <= inlier_px against it.  Best = most inliers, then the larger sum of the
+ *     inliers' confidences (f32, ascending view position), then the first pair.  Best count < 2:
+ *     xyz NaN, mask 0, errors NaN.  Otherwise the final DLT over the best inlier set: mask = that
+ *     set, and the errors of all valid views are those against the final float32 point (w = 1).
+ *   Errors of invalid views are NaN.
+ * The float32 xyz equals, bit for bit, OpenCV 4.9's triangulation (Jacobi SVD DLT +
+ * convertPointsFromHomogeneous) over exactly the masked views in ascending position.
+ *
+ * inlier_px finite and > 0; min_conf not NaN.
+ * out_xyz_dev  : [n_points][3] float32.
+ * out_mask_dev : [n_points] uint8, bit i = view i (cam_idx[i]) used.
+ * out_err_dev  : optional [n_points][n_cam_idx] float32 (may be NULL).
+ * ------------------------------------------------------------------------- */
+int mvp_triangulate_robust(const float* kpts_dev, int64_t n_points, int V, const double* cams_dev, int n_cams,
+                           const int* cam_idx_host, int n_cam_idx, float inlier_px, float min_conf,
+                           float* out_xyz_dev, uint8_t* out_mask_dev /* [n], bit i = view i used */,
+                           float* out_err_dev /* [n][n_cam_idx], may be NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * mvp_triangulate_points_f64 — replaces utils.triangulate_points (utils.py:1277-1336)
  * called with float64 keypoints, as the extrinsic branch does on its Gaussian samples
  * (pose_refinement.py:811): OpenCV keeps CV_64F through undistortPoints, triangulatePoints

@@ -40,6 +40,8 @@ SIGNATURES = {
     "mvp_camera_pack": (c_int, [P(c_double), P(c_double), P(c_double), P(c_double), P(c_double)]),
     "mvp_triangulate": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_int,
                                 c_void_p, c_void_p, c_void_p]),
+    "mvp_triangulate_robust": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_float, c_float,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_points_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_fallback_total": (c_int, [c_void_p, P(ctypes.c_ulonglong)]),
     "mvp_mp4v_create": (c_int, [c_void_p, c_size_t, P(c_void_p), P(c_int), P(c_int)]),

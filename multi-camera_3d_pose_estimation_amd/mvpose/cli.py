@@ -54,7 +54,13 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                              model_yaml="./model_paths.yaml", calibration_settings_yaml="./calibration_settings.yaml",
                              checkerboard_display_parameter_yaml="./checkerboard_display_parameters.yaml",
                              origin_camera_idx=0, script_path=None, project_dir="", recording_length_seconds=10,
-                             keep_unsynced_files=False):
+                             keep_unsynced_files=False, triangulation="reference", inlier_px=10.0,
+                             min_confidence=0.0):
+    """triangulation / inlier_px / min_confidence (no reference counterpart): "reference" (default)
+    triangulates from cameras [0, 1] and writes exactly the reference's files; "all_views" and
+    "robust" use every camera in camera_names (estimate_pose_from_video), record the three
+    settings in recording_log.yaml and also write kpts_3d_inliers.npy (T,17,V) bool and, for
+    "robust", kpts_3d_reproj_err.npy (T,17,V) f32."""
     from .pose_estimation import estimate_pose_from_video
     if project_dir:
         os.chdir(project_dir)
@@ -68,15 +74,27 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
         raise NotImplementedError("audio-based video synchronisation is outside the GPU hot path: pass "
                                   "already synchronised recordings (omit --synchronize_video)")
     recordings_folder = os.path.dirname(recording_paths[0])
-    kpts_2d, heatmaps, kpts_3d = estimate_pose_from_video(
+    robust_kw = {}
+    if triangulation != "reference":
+        robust_kw = {"triangulation": triangulation, "inlier_px": inlier_px, "min_conf": min_confidence,
+                     "return_info": True}
+    kpts_2d, heatmaps, kpts_3d, *info = estimate_pose_from_video(
         camera_names, recording_paths, estimator_model, detector_model=detector_model, model_yaml=model_yaml,
         start_end_frames=[0, -1], confidence=0,
-        extrinsic_params_dir=os.path.join(configuration_dir, "extrinsic_camera_parameters"))
+        extrinsic_params_dir=os.path.join(configuration_dir, "extrinsic_camera_parameters"), **robust_kw)
     log = {"recording_paths": [str(p) for p in recording_paths],
            "kpts_2d": str(os.path.join(recordings_folder, "kpts_2d.npy")),
            "heatmaps_2d": str(os.path.join(recordings_folder, "heatmaps_2d.npy")),
            "kpts_3d": str(os.path.join(recordings_folder, "kpts_3d.npy")),
            "estimator_model": estimator_model, "detector_model": detector_model}
+    extra = {}
+    if triangulation != "reference":
+        log.update({"triangulation": triangulation, "inlier_px": float(inlier_px),
+                    "min_confidence": float(min_confidence)})
+        for key, name in (("inliers", "kpts_3d_inliers"), ("reproj_err", "kpts_3d_reproj_err")):
+            if info[0][key] is not None:
+                log[name] = str(os.path.join(recordings_folder, name + ".npy"))
+                extra[name] = info[0][key]
     with open(os.path.join(recordings_folder, "recording_log.yaml"), "w") as f:
         yaml.dump(log, f)
     if kpts_2d is not None:
@@ -85,11 +103,14 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
         np.save(log["heatmaps_2d"], heatmaps)
     if kpts_3d is not None:
         np.save(log["kpts_3d"], kpts_3d)
+    for name, arr in extra.items():
+        np.save(log[name], arr)
     return log
 
 
-def record_and_estimate_pose_parser():
-    """Flags of record_and_estimate_pose.py:63-78."""
+def record_and_estimate_pose_parser(extensions=False):
+    """Flags of record_and_estimate_pose.py:63-78; extensions=True (what the command line uses)
+    adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence."""
     p = argparse.ArgumentParser()
     p.add_argument("--camera_names", nargs="+", required=True, help="List of camera names")
     p.add_argument("--estimator_model")
@@ -105,11 +126,15 @@ def record_and_estimate_pose_parser():
     p.add_argument("--project_dir")
     p.add_argument("--recording_length_seconds", type=int)
     p.add_argument("--keep_unsynced_files", action="store_true")
+    if extensions:   # N-view triangulation (estimate_pose_from_video's `triangulation`)
+        p.add_argument("--triangulation", choices=["reference", "all_views", "robust"])
+        p.add_argument("--inlier_px", type=float)
+        p.add_argument("--min_confidence", type=float)
     return p
 
 
 def record_and_estimate_pose_main(argv=None):
-    args = record_and_estimate_pose_parser().parse_args(argv)
+    args = record_and_estimate_pose_parser(extensions=True).parse_args(argv)
     return record_and_estimate_pose(**{k: v for k, v in vars(args).items() if v is not None})
 
 

@@ -20,6 +20,7 @@ TRI_REFERENCE = 0
 TRI_ALL_VIEWS = 1
 TRI_EXACT_JACOBI = 0x10  # mode flag: exact Jacobi SVD for every point (mvpose.h)
 TRI_TOLERANCE = 0x20     # mode flag: throughput solver validated to <= 1e-4 world units (mvpose.h)
+TRI_ROBUST = 2           # Python-level only (MultiViewPipeline mode): triangulate_robust, never an mvp_triangulate mode
 
 
 def _stream(device=None) -> ctypes.c_void_p:
@@ -116,6 +117,39 @@ def triangulate(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int] =
     call("mvp_triangulate", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, len(cam_idx), int(mode),
          _ptr(out), _ptr(xyzw) if xyzw is not None else None, _stream(kpts.device))
     return (out, xyzw) if return_xyzw else out
+
+
+def triangulate_robust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], inlier_px: float = 10.0,
+                       min_conf: float = 0.0, return_err: bool = True):
+    """N-view triangulation with per-point outlier-view rejection (mvp_triangulate_robust; the
+    algorithm is stated in include/mvpose.h; no reference counterpart).
+
+    kpts (..., 3, V) float32 on GPU, cams (n_cams, 40) float64 on GPU; view i reads column
+    cam_idx[i] with camera cam_idx[i]'s parameters, as TRI_ALL_VIEWS does.  Returns
+    (xyz (..., 3) float32, inliers (..., NV) bool, err (..., NV) float32 or None): the point
+    triangulated from its inlier views (bit-identical to the all-views DLT over exactly those
+    views; NaN where fewer than two views agree within inlier_px), the views used, and every
+    valid view's reprojection error in undistorted pixels against the returned point (+inf
+    behind the camera, NaN for views that are not finite or below min_conf)."""
+    _require(kpts, torch.float32, "kpts")
+    _require(cams, torch.float64, "cams")
+    if kpts.dim() < 2 or kpts.shape[-2] != 3:
+        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
+    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
+        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
+    V = kpts.shape[-1]
+    lead = tuple(kpts.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    nv = len(cam_idx)
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
+    bits = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
+    err = torch.empty(lead + (nv,), dtype=torch.float32, device=kpts.device) if return_err else None
+    ci = (ctypes.c_int * nv)(*[int(c) for c in cam_idx])
+    call("mvp_triangulate_robust", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
+         float(min_conf), _ptr(out), _ptr(bits), _ptr(err) if err is not None else None, _stream(kpts.device))
+    shifts = torch.arange(nv, dtype=torch.uint8, device=kpts.device)
+    inliers = ((bits.unsqueeze(-1) >> shifts) & 1).to(torch.bool)
+    return out, inliers, err
 
 
 def triangulate_fallback_total(device=None) -> int:

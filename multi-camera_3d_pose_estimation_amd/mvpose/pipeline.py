@@ -24,7 +24,7 @@ from .hrnet import N_JOINTS
 class MultiViewPipeline:
     def __init__(self, camera_params, estimator: BatchPoseEstimator | None = None, camera_indices=(0, 1),
                  mode: int = ops.TRI_REFERENCE, device="cuda", detector=None, bbox_thr: float = 0.3,
-                 tri_solver: str = "tolerance", **estimator_kw):
+                 tri_solver: str = "tolerance", inlier_px: float = 10.0, min_conf: float = 0.0, **estimator_kw):
         """camera_params: {camera key: [K, R, T, dist]} (utils.get_params_from_name order),
         keys 0..V-1 as the reference assumes (pose_estimation.py:276-280).
         detector: an mvpose.rtmdet.RTMDetector run on every camera-frame before the crops
@@ -33,10 +33,18 @@ class MultiViewPipeline:
         tri_solver: "tolerance" (default: MVP_TRI_TOLERANCE, <= 1e-4 world units against
         OpenCV's rounding sequence, bit-identical on almost every point) or "reference_compat"
         (OpenCV 4.9's fp64 rounding sequence, QR + inverse iteration with the Jacobi
-        restatement where that has not converged)."""
+        restatement where that has not converged).
+        mode=ops.TRI_ROBUST: ops.triangulate_robust over camera_indices (outlier views rejected
+        per point at inlier_px undistorted pixels, views below min_conf ignored); process() then
+        also returns tri_inliers (T, 17, NV) bool and tri_reproj_err (T, 17, NV) float32.
+        tri_solver does not apply in this mode."""
         if tri_solver not in ("tolerance", "reference_compat"):
             raise ValueError(f"tri_solver {tri_solver!r}: 'tolerance' or 'reference_compat'")
+        if mode == ops.TRI_ROBUST and tri_solver != "tolerance":
+            raise ValueError("tri_solver does not apply to mode=ops.TRI_ROBUST: leave it at its default")
         self.tri_solver = tri_solver
+        self.inlier_px = float(inlier_px)
+        self.min_conf = float(min_conf)
         self.detector = detector
         self.bbox_thr = bbox_thr
         self._best = None
@@ -78,6 +86,10 @@ class MultiViewPipeline:
             out["moments_done"] = r["moments_done"]
         else:
             out.pop("moments_done", None)
+        if self.mode == ops.TRI_ROBUST:
+            out["kpts_3d"], out["tri_inliers"], out["tri_reproj_err"] = ops.triangulate_robust(
+                out["kpts_2d"], self.cams, self.camera_indices, inlier_px=self.inlier_px, min_conf=self.min_conf)
+            return out
         out["kpts_3d"] = ops.triangulate(out["kpts_2d"], self.cams, self.camera_indices, mode=self.mode,
                                          out=out.get("kpts_3d"), tolerance=self.tri_solver == "tolerance")
         return out

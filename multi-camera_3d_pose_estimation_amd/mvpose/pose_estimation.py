@@ -31,10 +31,24 @@ from .estimator import BatchPoseEstimator
 from .hrnet import N_JOINTS
 
 
+TRIANGULATION_METHODS = ("reference", "all_views", "robust")
+
+
 def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices=None,
-                ignore_nonlinear_distortions=False, device=None):
+                ignore_nonlinear_distortions=False, device=None, method="reference", inlier_px=10.0,
+                min_conf=0.0, return_info=False):
     """camera_params {key: [K, R, T, dist]} (get_params_from_name order), all_kpts_2d
-    (T, J, 3, V) -> (T, J, 3) float32 numpy (float64 if world_trans_rot is given)."""
+    (T, J, 3, V) -> (T, J, 3) float32 numpy (float64 if world_trans_rot is given).
+
+    method: "reference" (default: the reference's rule, the two highest-confidence listed
+    cameras, parameters keyed by selection position), "all_views" (one DLT over every listed
+    camera, each with its own parameters) or "robust" (ops.triangulate_robust: all listed
+    cameras with per-point outlier-view rejection at inlier_px undistorted pixels, views below
+    min_conf ignored).  return_info: also return {"inliers": (T, J, NV) bool — the listed
+    views that entered each point's solve (None for "reference": the selection is internal),
+    "reproj_err": (T, J, NV) float32 (method "robust" only, else None)}."""
+    if method not in TRIANGULATION_METHODS:
+        raise ValueError(f"method {method!r}: one of {TRIANGULATION_METHODS}")
     dev = torch.device(device if device is not None else "cuda")
     keys = list(camera_params.keys())
     params = {}
@@ -46,11 +60,22 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     positions = [keys.index(c) for c in camera_indices]
     kp = torch.as_tensor(np.ascontiguousarray(np.asarray(all_kpts_2d, dtype=np.float32)), device=dev)
     cams = torch.tensor(ops.pack_cameras(params), device=dev)
-    out = ops.triangulate(kp, cams, positions, mode=ops.TRI_REFERENCE).cpu().numpy()
+    info = {"inliers": None, "reproj_err": None}
+    if method == "robust":
+        xyz, inliers, err = ops.triangulate_robust(kp, cams, positions, inlier_px=inlier_px, min_conf=min_conf,
+                                                   return_err=return_info)
+        out = xyz.cpu().numpy()
+        info["inliers"] = inliers.cpu().numpy()
+        info["reproj_err"] = err.cpu().numpy() if err is not None else None
+    elif method == "all_views":
+        out = ops.triangulate(kp, cams, positions, mode=ops.TRI_ALL_VIEWS).cpu().numpy()
+        info["inliers"] = np.ones(out.shape[:-1] + (len(positions),), dtype=bool)
+    else:
+        out = ops.triangulate(kp, cams, positions, mode=ops.TRI_REFERENCE).cpu().numpy()
     if world_trans_rot is not None:
         R_W0, _ = world_trans_rot
         out = np.einsum("ij,tpj->tpi", np.linalg.inv(R_W0), out)
-    return out
+    return (out, info) if return_info else out
 
 
 def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17)):
@@ -289,9 +314,17 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
 
 def estimate_pose_from_video(camera_names, recording_paths, model, detector_model="coco_base", model_yaml="",
                              start_end_frames=(0, -1), confidence=0, extrinsic_params_dir="",
-                             recompute_kpts_2d=True):
+                             recompute_kpts_2d=True, triangulation="reference", inlier_px=10.0, min_conf=0.0,
+                             return_info=False):
     """pose_estimation.py:259-327.  recompute_kpts_2d replaces the reference's interactive
-    y/n prompt when kpts_2d.npy already exists (:287-289)."""
+    y/n prompt when kpts_2d.npy already exists (:287-289).
+
+    triangulation: "reference" (default) triangulates from cameras [0, 1] as the reference
+    hard-codes (:319); "all_views" and "robust" (get_pose_3D's methods, with inlier_px and
+    min_conf) list every camera in camera_names.  return_info appends get_pose_3D's info
+    dict to the returned tuple."""
+    if triangulation not in TRIANGULATION_METHODS:
+        raise ValueError(f"triangulation {triangulation!r}: one of {TRIANGULATION_METHODS}")
     index_name, _origin = geometry.load_camera_names(extrinsic_params_dir)
     name_index = {v: k for k, v in index_name.items()}
     camera_indices = [name_index[n] for n in camera_names]
@@ -313,5 +346,14 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
                                     frame_hw=tuple(frames[camera_indices[0]].shape[1:3]))
         kpts_2d, heatmaps = run_pose_est(model, confidence=confidence, camera_indices=camera_indices,
                                          recording_paths=frames, start_end_frames=(0, None))
-    kpts_3d = get_pose_3D(camera_params, kpts_2d, camera_indices=[0, 1])
+    if triangulation == "reference":
+        listed = [0, 1]
+        kpts_3d = get_pose_3D(camera_params, kpts_2d, camera_indices=listed)
+        info = {"inliers": None, "reproj_err": None}
+    else:
+        listed = list(range(len(camera_names)))
+        kpts_3d, info = get_pose_3D(camera_params, kpts_2d, camera_indices=listed, method=triangulation,
+                                    inlier_px=inlier_px, min_conf=min_conf, return_info=True)
+    if return_info:
+        return kpts_2d, heatmaps, kpts_3d, info
     return kpts_2d, heatmaps, kpts_3d
