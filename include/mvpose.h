@@ -133,6 +133,65 @@ int mvp_triangulate_robust(const float* kpts_dev, int64_t n_points, int V, const
                            float* out_err_dev /* [n][n_cam_idx], may be NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * mvp_triangulate_refine — maximum-likelihood N-view triangulation from a seed, with the point's
+ * 3D covariance.  No reference counterpart.  (The reference's SGD scores every camera against
+ * camera 0's Gaussian, finding F5; here each camera is scored against its own.)
+ *
+ * kpts_dev, cams_dev, cam_idx_host / n_cam_idx as for mvp_triangulate_robust: view i reads column
+ * cam_idx[i] and the parameters of camera cam_idx[i]; 2 <= n_cam_idx <= 8.  Everything is fp64.
+ *   Used view: its bit in mask_dev[p] is set (or mask_dev is NULL); x and y finite; conf not NaN
+ *     and conf >= min_conf; with MVP_REFINE_W_GAUSS also: its six Gaussian numbers are finite and
+ *     not all zero (all zeros is the record of an empty heatmap), and
+ *     S = [[vxx, vxy], [vxy, vyy]] + cov_floor·I is positive definite (S00 > 0 and det S > 0).
+ *   Observation z_i and weight W_i of a used view:
+ *     MVP_REFINE_W_UNIT   z = (x, y) of kpts,  W = I
+ *     MVP_REFINE_W_CONF   z = (x, y) of kpts,  W = conf·I
+ *     MVP_REFINE_W_GAUSS  z = (mx, my),        W = S⁻¹
+ *     The Gaussian of point p = t·J + j in view i is gauss_dev[t][cam_idx[i]][j] =
+ *     [mx, my, vxx, vxy, vxy, vyy] (the heatmaps_2d layout; the first vxy is the one read).
+ *   Forward model pi_i(X): P = R·X + T, which requires P_z > 0; (x, y) = (P_x, P_y) / P_z;
+ *     r2 = x² + y², radial = 1 + k1·r2 + k2·r2² + k3·r2³,
+ *     xd = x·radial + 2·p1·x·y + p2·(r2 + 2x²), yd = y·radial + p1·(r2 + 2y²) + 2·p2·x·y;
+ *     pixel = (K00·xd + K01·yd + K02, K11·yd + K12).  Observations are raw, distorted pixels:
+ *     nothing is undistorted.
+ *   Cost f(X) = ½ Σ r_iᵀ W_i r_i over the used views, r_i = pi_i(X) - z_i; +inf when any used view
+ *     has P_z <= 0.
+ *   Solver: Levenberg-Marquardt on the 3x3 normal equations with analytic Jacobians J_i = d pi_i /
+ *     dX: H = Σ J_iᵀ W_i J_i, g = Σ J_iᵀ W_i r_i, lambda = 1e-3 at the start.  A trial solves
+ *     (H + lambda·diag H)·delta = -g by Cholesky and is accepted when f(X + delta) is finite and
+ *     <= f(X): then X <- X + delta and lambda <- max(lambda/10, 1e-12); otherwise lambda <-
+ *     10·lambda.  The point has converged at the first trial whose proposed step satisfies
+ *     |delta| <= tol·(|X| + tol), X being the point the step was proposed from, whether the trial
+ *     is accepted or not (an accepted step is applied first).  At most max_iter trials.
+ *   Failure: fewer than 2 used views; a seed that is not finite; f at the seed not finite; a
+ *     Cholesky pivot of a trial's damped matrix that is not > 0.  A failed point returns the seed's
+ *     bits as xyz, NaN cov and cost, status 0x80: a refined point is never less defined than its seed.
+ *
+ * xyz0_dev       : [n_points][3] float32 seed (any triangulator's output).
+ * mask_dev       : optional [n_points] uint8, bit i = view i may be used (mvp_triangulate_robust's
+ *                  out_mask); NULL = every listed view.
+ * weights        : MVP_REFINE_W_*.  gauss_dev / J: [n_points/J][V][J][6] float64, required for
+ *                  MVP_REFINE_W_GAUSS (J > 0 dividing n_points), ignored otherwise.
+ * min_conf not NaN; cov_floor >= 0 (pixels², not NaN); 0 <= max_iter <= 63; tol finite, > 0.
+ * out_xyz_dev    : [n_points][3] float32, the final X.
+ * out_cov_dev    : optional [n_points][6] float32 (xx, xy, xz, yy, yz, zz): the inverse of the
+ *                  undamped H at the final X, world units²; NaN when that H is not positive definite.
+ * out_cost_dev   : optional [n_points] float32, f at the final X.
+ * out_status_dev : optional [n_points] uint8: bits 0-5 the number of trials, 0x40 no trial met the
+ *                  convergence test (max_iter = 0 included), 0x80 failed (then exactly 0x80).
+ * With max_iter = 0 the call returns the seed, with cov and cost evaluated at the seed.
+ * ------------------------------------------------------------------------- */
+#define MVP_REFINE_W_UNIT 0
+#define MVP_REFINE_W_CONF 1
+#define MVP_REFINE_W_GAUSS 2
+
+int mvp_triangulate_refine(const float* kpts_dev, int64_t n_points, int V, const double* cams_dev, int n_cams,
+                           const int* cam_idx_host, int n_cam_idx, const float* xyz0_dev, const uint8_t* mask_dev,
+                           int weights, const double* gauss_dev, int J, float min_conf, float cov_floor,
+                           int max_iter, double tol, float* out_xyz_dev, float* out_cov_dev, float* out_cost_dev,
+                           uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * mvp_triangulate_points_f64 — replaces utils.triangulate_points (utils.py:1277-1336)
  * called with float64 keypoints, as the extrinsic branch does on its Gaussian samples
  * (pose_refinement.py:811): OpenCV keeps CV_64F through undistortPoints, triangulatePoints

@@ -42,6 +42,9 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_robust": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_float, c_float,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_triangulate_refine": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p, c_void_p,
+                                       c_int, c_void_p, c_int, c_float, c_float, c_int, c_double, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_points_f64": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_fallback_total": (c_int, [c_void_p, P(ctypes.c_ulonglong)]),
     "mvp_mp4v_create": (c_int, [c_void_p, c_size_t, P(c_void_p), P(c_int), P(c_int)]),

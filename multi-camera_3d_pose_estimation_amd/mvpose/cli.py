@@ -55,12 +55,18 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                              checkerboard_display_parameter_yaml="./checkerboard_display_parameters.yaml",
                              origin_camera_idx=0, script_path=None, project_dir="", recording_length_seconds=10,
                              keep_unsynced_files=False, triangulation="reference", inlier_px=10.0,
-                             min_confidence=0.0):
+                             min_confidence=0.0, refine=None, cov_floor=1.0):
     """triangulation / inlier_px / min_confidence (no reference counterpart): "reference" (default)
     triangulates from cameras [0, 1] and writes exactly the reference's files; "all_views" and
     "robust" use every camera in camera_names (estimate_pose_from_video), record the three
     settings in recording_log.yaml and also write kpts_3d_inliers.npy (T,17,V) bool and, for
-    "robust", kpts_3d_reproj_err.npy (T,17,V) f32."""
+    "robust", kpts_3d_reproj_err.npy (T,17,V) f32.
+    refine / cov_floor (no reference counterpart): "unit", "conf" or "heatmap" refines the
+    triangulated points by maximum likelihood (get_pose_3D); kpts_3d.npy then holds the refined
+    points, and kpts_3d_seed.npy, kpts_3d_cov.npy (T,17,3,3) f32 and kpts_3d_refine_status.npy
+    (T,17) uint8 are written too, the two settings recorded in recording_log.yaml."""
+    if refine not in (None, "unit", "conf", "heatmap"):
+        raise ValueError(f"refine {refine!r}: None, 'unit', 'conf' or 'heatmap'")
     from .pose_estimation import estimate_pose_from_video
     if project_dir:
         os.chdir(project_dir)
@@ -78,6 +84,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
     if triangulation != "reference":
         robust_kw = {"triangulation": triangulation, "inlier_px": inlier_px, "min_conf": min_confidence,
                      "return_info": True}
+    if refine is not None:
+        robust_kw.update({"refine": refine, "cov_floor": cov_floor, "return_info": True})
     kpts_2d, heatmaps, kpts_3d, *info = estimate_pose_from_video(
         camera_names, recording_paths, estimator_model, detector_model=detector_model, model_yaml=model_yaml,
         start_end_frames=[0, -1], confidence=0,
@@ -95,6 +103,11 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
             if info[0][key] is not None:
                 log[name] = str(os.path.join(recordings_folder, name + ".npy"))
                 extra[name] = info[0][key]
+    if refine is not None:
+        log.update({"refine": refine, "cov_floor": float(cov_floor)})
+        for key, name in (("seed", "kpts_3d_seed"), ("cov", "kpts_3d_cov"), ("refine_status", "kpts_3d_refine_status")):
+            log[name] = str(os.path.join(recordings_folder, name + ".npy"))
+            extra[name] = info[0][key]
     with open(os.path.join(recordings_folder, "recording_log.yaml"), "w") as f:
         yaml.dump(log, f)
     if kpts_2d is not None:
@@ -110,7 +123,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
 
 def record_and_estimate_pose_parser(extensions=False):
     """Flags of record_and_estimate_pose.py:63-78; extensions=True (what the command line uses)
-    adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence."""
+    adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence,
+    --refine, --cov_floor."""
     p = argparse.ArgumentParser()
     p.add_argument("--camera_names", nargs="+", required=True, help="List of camera names")
     p.add_argument("--estimator_model")
@@ -130,6 +144,8 @@ def record_and_estimate_pose_parser(extensions=False):
         p.add_argument("--triangulation", choices=["reference", "all_views", "robust"])
         p.add_argument("--inlier_px", type=float)
         p.add_argument("--min_confidence", type=float)
+        p.add_argument("--refine", choices=["unit", "conf", "heatmap"])   # maximum-likelihood refinement
+        p.add_argument("--cov_floor", type=float)
     return p
 
 

@@ -21,6 +21,10 @@ TRI_ALL_VIEWS = 1
 TRI_EXACT_JACOBI = 0x10  # mode flag: exact Jacobi SVD for every point (mvpose.h)
 TRI_TOLERANCE = 0x20     # mode flag: throughput solver validated to <= 1e-4 world units (mvpose.h)
 TRI_ROBUST = 2           # Python-level only (MultiViewPipeline mode): triangulate_robust, never an mvp_triangulate mode
+REFINE_W_UNIT = 0        # mvp_triangulate_refine weights (mvpose.h MVP_REFINE_W_*)
+REFINE_W_CONF = 1
+REFINE_W_GAUSS = 2
+REFINE_WEIGHTS = {"unit": REFINE_W_UNIT, "conf": REFINE_W_CONF, "heatmap": REFINE_W_GAUSS}
 
 
 def _stream(device=None) -> ctypes.c_void_p:
@@ -150,6 +154,69 @@ def triangulate_robust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     shifts = torch.arange(nv, dtype=torch.uint8, device=kpts.device)
     inliers = ((bits.unsqueeze(-1) >> shifts) & 1).to(torch.bool)
     return out, inliers, err
+
+
+def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz0: torch.Tensor, *,
+                       weights: str = "unit", gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None,
+                       min_conf: float = 0.0, cov_floor: float = 1.0, max_iter: int = 10, tol: float = 1e-7):
+    """Maximum-likelihood refinement of triangulated points with their 3D covariance
+    (mvp_triangulate_refine; the algorithm is stated in include/mvpose.h; no reference counterpart).
+
+    kpts (..., 3, V) float32, cams (n_cams, 40) float64, cam_idx as for triangulate_robust; xyz0
+    (..., 3) float32 seed from any triangulator.  weights: "unit" (every view alike), "conf" (the
+    keypoint confidences) or "heatmap" (each view's own 2D Gaussian: gauss (T, V, J, 6) float64,
+    the heatmaps_2d layout, with kpts (T, J, 3, V); cov_floor px² is added to its variances).
+    mask: (..., NV) bool, the views that may be used (triangulate_robust's inliers), or None.
+    Levenberg-Marquardt on the Mahalanobis reprojection error of the raw, distorted pixels, at
+    most max_iter trials, converged at a step <= tol·(|X| + tol).  Returns (xyz (..., 3) float32,
+    cov (..., 3, 3) float32 symmetric, world units², cost (...) float32, status (...) uint8: bits
+    0-5 trials, 0x40 not converged, 0x80 failed).  A failed point (fewer than 2 usable views, a
+    seed that is not finite or behind a camera) returns its seed, NaN cov and cost.  With equal
+    isotropic noise in every view this does not beat the DLT seed: the gain is in the weighting
+    and in the covariance."""
+    if weights not in REFINE_WEIGHTS:
+        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
+    _require(kpts, torch.float32, "kpts")
+    _require(cams, torch.float64, "cams")
+    _require(xyz0, torch.float32, "xyz0")
+    if kpts.dim() < 2 or kpts.shape[-2] != 3:
+        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
+    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
+        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
+    V = kpts.shape[-1]
+    lead = tuple(kpts.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    nv = len(cam_idx)
+    if tuple(xyz0.shape) != lead + (3,):
+        raise ValueError(f"xyz0 must be {lead + (3,)}, got {tuple(xyz0.shape)}")
+    J = 0
+    if weights == "heatmap":
+        if gauss is None:
+            raise ValueError('weights="heatmap" needs gauss, the (T, V, J, 6) float64 heatmap Gaussians')
+        _require(gauss, torch.float64, "gauss")
+        if len(lead) != 2 or tuple(gauss.shape) != (lead[0], V, lead[1], 6):
+            raise ValueError(f"gauss must be (T, V, J, 6) = {(lead[0] if lead else None, V, lead[-1] if lead else None, 6)} "
+                             f"for kpts (T, J, 3, V), got {tuple(gauss.shape)}")
+        J = lead[1]
+    bits = None
+    if mask is not None:
+        _require(mask, torch.bool, "mask")
+        if tuple(mask.shape) != lead + (nv,):
+            raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
+        place = torch.tensor([1 << i for i in range(nv)], dtype=torch.int32, device=kpts.device)
+        bits = (mask.to(torch.int32) * place).sum(-1).to(torch.uint8).contiguous()
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
+    cov6 = torch.empty(lead + (6,), dtype=torch.float32, device=kpts.device)
+    cost = torch.empty(lead, dtype=torch.float32, device=kpts.device)
+    status = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
+    ci = (ctypes.c_int * nv)(*[int(c) for c in cam_idx])
+    call("mvp_triangulate_refine", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor), int(max_iter),
+         float(tol), _ptr(out), _ptr(cov6), _ptr(cost), _ptr(status), _stream(kpts.device))
+    sym = torch.tensor([0, 1, 2, 1, 3, 4, 2, 4, 5], device=kpts.device)
+    cov = cov6.index_select(-1, sym).reshape(lead + (3, 3))
+    return out, cov, cost, status
 
 
 def triangulate_fallback_total(device=None) -> int:

@@ -6,6 +6,9 @@ process(frames (T, V, H, W, 3) uint8 on GPU) returns, device-resident:
     kpts_2d     (T, 17, 3, V) float32   [x, y, score] per camera   (pose_estimation.py:135)
     heatmaps_2d (T, V, 17, 6) float64   [mx, my, vxx, vxy, vxy, vyy] (mmpose_pose_estimation.py:208-210)
     kpts_3d     (T, 17, 3)    float32   triangulated                 (pose_estimation.py:319-322)
+With refine= (no reference counterpart) kpts_3d holds the maximum-likelihood refinement of the
+triangulated points and kpts_3d_seed, kpts_3d_cov (T, 17, 3, 3), tri_refine_cost and
+tri_refine_status come with it (ops.triangulate_refine).
 
 process(..., overlap_moments=True) computes heatmaps_2d on a side stream beside the
 next batch's backbone (triangulation reads only kpts_2d); call wait(out) before reading
@@ -24,7 +27,8 @@ from .hrnet import N_JOINTS
 class MultiViewPipeline:
     def __init__(self, camera_params, estimator: BatchPoseEstimator | None = None, camera_indices=(0, 1),
                  mode: int = ops.TRI_REFERENCE, device="cuda", detector=None, bbox_thr: float = 0.3,
-                 tri_solver: str = "tolerance", inlier_px: float = 10.0, min_conf: float = 0.0, **estimator_kw):
+                 tri_solver: str = "tolerance", inlier_px: float = 10.0, min_conf: float = 0.0,
+                 refine: str | None = None, cov_floor: float = 1.0, **estimator_kw):
         """camera_params: {camera key: [K, R, T, dist]} (utils.get_params_from_name order),
         keys 0..V-1 as the reference assumes (pose_estimation.py:276-280).
         detector: an mvpose.rtmdet.RTMDetector run on every camera-frame before the crops
@@ -37,7 +41,16 @@ class MultiViewPipeline:
         mode=ops.TRI_ROBUST: ops.triangulate_robust over camera_indices (outlier views rejected
         per point at inlier_px undistorted pixels, views below min_conf ignored); process() then
         also returns tri_inliers (T, 17, NV) bool and tri_reproj_err (T, 17, NV) float32.
-        tri_solver does not apply in this mode."""
+        tri_solver does not apply in this mode.
+        refine: None (default: process() as without it) or "unit" / "conf" / "heatmap": the mode's
+        points seed ops.triangulate_refine over camera_indices (TRI_ROBUST: over each point's
+        inliers); "heatmap" weighs each view by its own heatmaps_2d Gaussian + cov_floor px².
+        process() then returns the refined points as kpts_3d and also kpts_3d_seed, kpts_3d_cov
+        (T, 17, 3, 3), tri_refine_cost (T, 17) and tri_refine_status (T, 17) uint8."""
+        if refine not in (None, "unit", "conf", "heatmap"):
+            raise ValueError(f"refine {refine!r}: None, 'unit', 'conf' or 'heatmap'")
+        self.refine = refine
+        self.cov_floor = float(cov_floor)
         if tri_solver not in ("tolerance", "reference_compat"):
             raise ValueError(f"tri_solver {tri_solver!r}: 'tolerance' or 'reference_compat'")
         if mode == ops.TRI_ROBUST and tri_solver != "tolerance":
@@ -89,9 +102,21 @@ class MultiViewPipeline:
         if self.mode == ops.TRI_ROBUST:
             out["kpts_3d"], out["tri_inliers"], out["tri_reproj_err"] = ops.triangulate_robust(
                 out["kpts_2d"], self.cams, self.camera_indices, inlier_px=self.inlier_px, min_conf=self.min_conf)
-            return out
+            return self._refine(out, out["tri_inliers"]) if self.refine is not None else out
+        if self.refine is not None:
+            out.pop("kpts_3d", None)       # the previous call's refined points are not a seed buffer
         out["kpts_3d"] = ops.triangulate(out["kpts_2d"], self.cams, self.camera_indices, mode=self.mode,
                                          out=out.get("kpts_3d"), tolerance=self.tri_solver == "tolerance")
+        return self._refine(out, None) if self.refine is not None else out
+
+    def _refine(self, out: dict, mask) -> dict:
+        if self.refine == "heatmap":
+            self.wait(out)                 # overlap_moments: the side stream's heatmaps_2d before they are read
+        out["kpts_3d_seed"] = out["kpts_3d"]
+        out["kpts_3d"], out["kpts_3d_cov"], out["tri_refine_cost"], out["tri_refine_status"] = ops.triangulate_refine(
+            out["kpts_2d"], self.cams, self.camera_indices, out["kpts_3d_seed"], weights=self.refine,
+            gauss=out["heatmaps_2d"] if self.refine == "heatmap" else None, mask=mask,
+            min_conf=self.min_conf if self.mode == ops.TRI_ROBUST else 0.0, cov_floor=self.cov_floor)
         return out
 
     def detect(self, flat: torch.Tensor) -> torch.Tensor:

@@ -32,11 +32,17 @@ from .hrnet import N_JOINTS
 
 
 TRIANGULATION_METHODS = ("reference", "all_views", "robust")
+REFINE_MODES = (None, "unit", "conf", "heatmap")
+
+
+def _check_refine(refine):
+    if refine not in REFINE_MODES:
+        raise ValueError(f"refine {refine!r}: one of {REFINE_MODES}")
 
 
 def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices=None,
                 ignore_nonlinear_distortions=False, device=None, method="reference", inlier_px=10.0,
-                min_conf=0.0, return_info=False):
+                min_conf=0.0, return_info=False, refine=None, heatmaps_2d=None, cov_floor=1.0):
     """camera_params {key: [K, R, T, dist]} (get_params_from_name order), all_kpts_2d
     (T, J, 3, V) -> (T, J, 3) float32 numpy (float64 if world_trans_rot is given).
 
@@ -46,9 +52,20 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     cameras with per-point outlier-view rejection at inlier_px undistorted pixels, views below
     min_conf ignored).  return_info: also return {"inliers": (T, J, NV) bool — the listed
     views that entered each point's solve (None for "reference": the selection is internal),
-    "reproj_err": (T, J, NV) float32 (method "robust" only, else None)}."""
+    "reproj_err": (T, J, NV) float32 (method "robust" only, else None)}.
+
+    refine: None (default) or "unit" / "conf" / "heatmap": the chosen method's points seed
+    ops.triangulate_refine (maximum-likelihood refinement over the listed cameras, for "robust"
+    over each point's inlier views; "heatmap" weighs every view by its own Gaussian of
+    heatmaps_2d (T, V, J, 6), with cov_floor px² added to the variances), and the refined points
+    are returned.  info then also holds "cov" (T, J, 3, 3) float32 (rotated with the points when
+    world_trans_rot is given), "refine_cost" (T, J), "refine_status" (T, J) uint8 and "seed"
+    (T, J, 3), the method's own points."""
     if method not in TRIANGULATION_METHODS:
         raise ValueError(f"method {method!r}: one of {TRIANGULATION_METHODS}")
+    _check_refine(refine)
+    if refine == "heatmap" and heatmaps_2d is None:
+        raise ValueError('refine="heatmap" needs heatmaps_2d, the (T, V, J, 6) heatmap Gaussians')
     dev = torch.device(device if device is not None else "cuda")
     keys = list(camera_params.keys())
     params = {}
@@ -61,20 +78,38 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     kp = torch.as_tensor(np.ascontiguousarray(np.asarray(all_kpts_2d, dtype=np.float32)), device=dev)
     cams = torch.tensor(ops.pack_cameras(params), device=dev)
     info = {"inliers": None, "reproj_err": None}
+    seed_dev = mask_dev = None
     if method == "robust":
         xyz, inliers, err = ops.triangulate_robust(kp, cams, positions, inlier_px=inlier_px, min_conf=min_conf,
                                                    return_err=return_info)
+        seed_dev, mask_dev = xyz, inliers
         out = xyz.cpu().numpy()
         info["inliers"] = inliers.cpu().numpy()
         info["reproj_err"] = err.cpu().numpy() if err is not None else None
     elif method == "all_views":
-        out = ops.triangulate(kp, cams, positions, mode=ops.TRI_ALL_VIEWS).cpu().numpy()
+        seed_dev = ops.triangulate(kp, cams, positions, mode=ops.TRI_ALL_VIEWS)
+        out = seed_dev.cpu().numpy()
         info["inliers"] = np.ones(out.shape[:-1] + (len(positions),), dtype=bool)
     else:
-        out = ops.triangulate(kp, cams, positions, mode=ops.TRI_REFERENCE).cpu().numpy()
+        seed_dev = ops.triangulate(kp, cams, positions, mode=ops.TRI_REFERENCE)
+        out = seed_dev.cpu().numpy()
+    if refine is not None:
+        gauss = None
+        if refine == "heatmap":
+            gauss = torch.as_tensor(np.ascontiguousarray(np.asarray(heatmaps_2d, dtype=np.float64)), device=dev)
+        xyz, cov, cost, status = ops.triangulate_refine(
+            kp, cams, positions, seed_dev, weights=refine, gauss=gauss, mask=mask_dev,
+            min_conf=min_conf if method == "robust" else 0.0, cov_floor=cov_floor)
+        info.update({"seed": out, "cov": cov.cpu().numpy(), "refine_cost": cost.cpu().numpy(),
+                     "refine_status": status.cpu().numpy()})
+        out = xyz.cpu().numpy()
     if world_trans_rot is not None:
         R_W0, _ = world_trans_rot
-        out = np.einsum("ij,tpj->tpi", np.linalg.inv(R_W0), out)
+        Ri = np.linalg.inv(R_W0)
+        out = np.einsum("ij,tpj->tpi", Ri, out)
+        if refine is not None:
+            info["seed"] = np.einsum("ij,tpj->tpi", Ri, info["seed"])
+            info["cov"] = np.einsum("ij,tpjk,lk->tpil", Ri, info["cov"], Ri)
     return (out, info) if return_info else out
 
 
@@ -315,16 +350,19 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
 def estimate_pose_from_video(camera_names, recording_paths, model, detector_model="coco_base", model_yaml="",
                              start_end_frames=(0, -1), confidence=0, extrinsic_params_dir="",
                              recompute_kpts_2d=True, triangulation="reference", inlier_px=10.0, min_conf=0.0,
-                             return_info=False):
+                             return_info=False, refine=None, cov_floor=1.0):
     """pose_estimation.py:259-327.  recompute_kpts_2d replaces the reference's interactive
     y/n prompt when kpts_2d.npy already exists (:287-289).
 
     triangulation: "reference" (default) triangulates from cameras [0, 1] as the reference
     hard-codes (:319); "all_views" and "robust" (get_pose_3D's methods, with inlier_px and
     min_conf) list every camera in camera_names.  return_info appends get_pose_3D's info
-    dict to the returned tuple."""
+    dict to the returned tuple.  refine / cov_floor: get_pose_3D's maximum-likelihood refinement
+    of the triangulated points ("heatmap" reads this run's heatmaps_2d, so it needs the 2D stage
+    to run: recompute_kpts_2d, or no kpts_2d.npy yet)."""
     if triangulation not in TRIANGULATION_METHODS:
         raise ValueError(f"triangulation {triangulation!r}: one of {TRIANGULATION_METHODS}")
+    _check_refine(refine)
     index_name, _origin = geometry.load_camera_names(extrinsic_params_dir)
     name_index = {v: k for k, v in index_name.items()}
     camera_indices = [name_index[n] for n in camera_names]
@@ -346,14 +384,15 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
                                     frame_hw=tuple(frames[camera_indices[0]].shape[1:3]))
         kpts_2d, heatmaps = run_pose_est(model, confidence=confidence, camera_indices=camera_indices,
                                          recording_paths=frames, start_end_frames=(0, None))
-    if triangulation == "reference":
+    if triangulation == "reference" and refine is None:
         listed = [0, 1]
         kpts_3d = get_pose_3D(camera_params, kpts_2d, camera_indices=listed)
         info = {"inliers": None, "reproj_err": None}
     else:
-        listed = list(range(len(camera_names)))
+        listed = [0, 1] if triangulation == "reference" else list(range(len(camera_names)))
         kpts_3d, info = get_pose_3D(camera_params, kpts_2d, camera_indices=listed, method=triangulation,
-                                    inlier_px=inlier_px, min_conf=min_conf, return_info=True)
+                                    inlier_px=inlier_px, min_conf=min_conf, return_info=True, refine=refine,
+                                    heatmaps_2d=heatmaps, cov_floor=cov_floor)
     if return_info:
         return kpts_2d, heatmaps, kpts_3d, info
     return kpts_2d, heatmaps, kpts_3d
