@@ -81,7 +81,7 @@ int mvp_camera_pack(const double* K_host, const double* dist5_host, const double
  * f32 roundings fall inside the error bound is re-solved on the exact path by a second launch).
  * The certification is EMPIRICAL, not a proof: the null vector's rounding-floor term uses
  * constants fitted on 1.4 M synthetic and random points (the exact Jacobi's own error measured
- * <= 0.025 eps*sqrt(trM/D2) where 0.2 is used, and D2/lambda3 <= 1.4; triangulate.hip
+ * <= 0.025 eps*sqrt(trM/D2) where 0.2 is used, and D2/lambda3 <= 1.4; tri_common.h
  * null_vector_delta2).  tests/test_triangulate_gpu.py also asserts bit-identity on adversarial rigs (tiny
  * baselines, points near the epipoles, near-parallel rays).  Pass MVP_TRI_EXACT_JACOBI where a
  * proof is required.

@@ -1,0 +1,290 @@
+// mvp_triangulate_refine: maximum-likelihood refinement of triangulated points with a 3D covariance
+// (shared device code in tri_common.h; map of the triangulation files in triangulate.hip).
+#pragma clang fp contract(off)
+
+#include "tri_common.h"
+
+namespace {
+
+// ----------------------------------------------------------------- maximum-likelihood refinement
+// mvp_triangulate_refine: Levenberg-Marquardt on the weighted reprojection error through the full
+// distortion model, from any triangulator's seed; the inverse Gauss-Newton Hessian is the point's
+// covariance (no reference counterpart; algorithm in mvpose.h).  Per lane, fp64, FMA contraction on
+// (no bit contract here):
+//   * the used views' observation (2) and weight (3 numbers) are parked in LDS, [view][lane]
+//     (bank-conflict free), as the robust kernel parks its views: the trial loop walks the views
+//     in a rolled loop, which a per-lane register array cannot serve without going to scratch
+//     (unrolled, the compiler hoists every view's camera record out of the trial loop: 256 VGPRs
+//     + 150 AGPRs at NV = 8);
+//   * the camera records are read through wave-uniform addresses straight from the parameter block
+//     (scalar loads, one view's record at a time);
+//   * ONE copy of the cost / gradient / Hessian evaluation inside the trial loop (trip 0 evaluates
+//     the seed); accept / reject is selects, and the loop is left on a wave ballot once every lane
+//     has converged, failed or used up max_iter — the pattern of triangulate_tol2_kernel.
+struct RefineCam {  // what one view's forward model reads of a camera record
+    double fx, skew, cx, fy, cy, k1, k2, p1, p2, k3, R[9], T[3];
+};
+
+__device__ __forceinline__ RefineCam refine_cam(const double* __restrict__ c) {
+    RefineCam r;
+    r.fx = c[0], r.skew = c[1], r.cx = c[2], r.fy = c[4], r.cy = c[5];
+    r.k1 = c[9], r.k2 = c[10], r.p1 = c[11], r.p2 = c[12], r.k3 = c[13];
+#pragma unroll
+    for (int k = 0; k < 9; k++) r.R[k] = c[14 + k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) r.T[k] = c[23 + k];
+    return r;
+}
+
+// One view's term of f, g (3) and H (xx, xy, xz, yy, yz, zz) at X, branch-free; false when the
+// point is not in front of the camera (the caller then drops the terms, which may be Inf / NaN).
+__device__ __forceinline__ bool refine_view_terms(const RefineCam& c, const double (&X)[3], double zx, double zy,
+                                                  double wxx, double wxy, double wyy, double& f, double (&g)[3],
+                                                  double (&H)[6]) {
+#pragma clang fp contract(fast)
+    const double Px = c.R[0] * X[0] + c.R[1] * X[1] + c.R[2] * X[2] + c.T[0];
+    const double Py = c.R[3] * X[0] + c.R[4] * X[1] + c.R[5] * X[2] + c.T[1];
+    const double Pz = c.R[6] * X[0] + c.R[7] * X[1] + c.R[8] * X[2] + c.T[2];
+    const double iz = 1.0 / Pz;
+    const double x = Px * iz, y = Py * iz;
+    const double r2 = x * x + y * y;
+    const double radial = 1 + r2 * (c.k1 + r2 * (c.k2 + r2 * c.k3));
+    const double drad = c.k1 + r2 * (2 * c.k2 + 3 * c.k3 * r2);  // d radial / d r2
+    const double xd = x * radial + 2 * c.p1 * x * y + c.p2 * (r2 + 2 * x * x);
+    const double yd = y * radial + c.p1 * (r2 + 2 * y * y) + 2 * c.p2 * x * y;
+    const double r0 = c.fx * xd + c.skew * yd + c.cx - zx;
+    const double r1 = c.fy * yd + c.cy - zy;
+    // d(xd, yd) / d(x, y): symmetric off-diagonal
+    const double dxx = radial + 2 * x * x * drad + 2 * c.p1 * y + 6 * c.p2 * x;
+    const double dxy = 2 * x * y * drad + 2 * c.p1 * x + 2 * c.p2 * y;
+    const double dyy = radial + 2 * y * y * drad + 6 * c.p1 * y + 2 * c.p2 * x;
+    const double a00 = c.fx * dxx + c.skew * dxy, a01 = c.fx * dxy + c.skew * dyy;
+    const double a10 = c.fy * dxy, a11 = c.fy * dyy;
+    double J0[3], J1[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const double m0 = (c.R[k] - x * c.R[6 + k]) * iz;  // d x / d X_k
+        const double m1 = (c.R[3 + k] - y * c.R[6 + k]) * iz;
+        J0[k] = a00 * m0 + a01 * m1;
+        J1[k] = a10 * m0 + a11 * m1;
+    }
+    const double wr0 = wxx * r0 + wxy * r1, wr1 = wxy * r0 + wyy * r1;
+    f += 0.5 * (r0 * wr0 + r1 * wr1);
+    double wj0[3], wj1[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        wj0[k] = wxx * J0[k] + wxy * J1[k];
+        wj1[k] = wxy * J0[k] + wyy * J1[k];
+        g[k] += J0[k] * wr0 + J1[k] * wr1;
+    }
+    H[0] += J0[0] * wj0[0] + J1[0] * wj1[0];
+    H[1] += J0[0] * wj0[1] + J1[0] * wj1[1];
+    H[2] += J0[0] * wj0[2] + J1[0] * wj1[2];
+    H[3] += J0[1] * wj0[1] + J1[1] * wj1[1];
+    H[4] += J0[1] * wj0[2] + J1[1] * wj1[2];
+    H[5] += J0[2] * wj0[2] + J1[2] * wj1[2];
+    return Pz > 0;
+}
+
+// Cholesky A = L·Lᵀ of the symmetric 3x3 (xx, xy, xz, yy, yz, zz); false on a non-positive (or
+// NaN) pivot.  L: l00, l10, l20, l11, l21, l22.
+__device__ __forceinline__ bool chol3(const double (&A)[6], double (&L)[6]) {
+#pragma clang fp contract(fast)
+    const double d0 = A[0];
+    L[0] = sqrt(d0);
+    L[1] = A[1] / L[0];
+    L[2] = A[2] / L[0];
+    const double d1 = A[3] - L[1] * L[1];
+    L[3] = sqrt(d1);
+    L[4] = (A[4] - L[2] * L[1]) / L[3];
+    const double d2 = A[5] - L[2] * L[2] - L[4] * L[4];
+    L[5] = sqrt(d2);
+    return (d0 > 0) && (d1 > 0) && (d2 > 0);
+}
+
+// x = A⁻¹ b from A's Cholesky factor.
+__device__ __forceinline__ void chol3_solve(const double (&L)[6], const double (&b)[3], double (&x)[3]) {
+#pragma clang fp contract(fast)
+    const double y0 = b[0] / L[0];
+    const double y1 = (b[1] - L[1] * y0) / L[3];
+    const double y2 = (b[2] - L[2] * y0 - L[4] * y1) / L[5];
+    x[2] = y2 / L[5];
+    x[1] = (y1 - L[4] * x[2]) / L[3];
+    x[0] = (y0 - L[1] * x[1] - L[2] * x[2]) / L[0];
+}
+
+template <int NV>
+__global__ __launch_bounds__(kBlock) void triangulate_refine_kernel(
+    const float* __restrict__ kpts, int64_t n, int V, const double* __restrict__ cams, CamIdx ci,
+    const float* __restrict__ xyz0, const uint8_t* __restrict__ mask, int weights, const double* __restrict__ gauss,
+    int J, float min_conf, float cov_floor, int max_iter, double tol, float* __restrict__ out_xyz,
+    float* __restrict__ out_cov, float* __restrict__ out_cost, uint8_t* __restrict__ out_status) {
+#pragma clang fp contract(fast)
+    __shared__ double s_zx[NV][kBlock], s_zy[NV][kBlock], s_wxx[NV][kBlock], s_wxy[NV][kBlock], s_wyy[NV][kBlock];
+    // the listed cameras (each < kMaxCams = 8) as nibbles of one scalar: the rolled view loop's index
+    unsigned cols = 0;
+#pragma unroll
+    for (int j = 0; j < NV; j++) cols |= (unsigned)ci.v[j] << (4 * j);
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int tid = threadIdx.x;
+    const float* __restrict__ kp = kpts + p * 3 * V;
+    const unsigned allowed = mask ? (unsigned)mask[p] : 0xFFu;
+    const int64_t gt = (weights == MVP_REFINE_W_GAUSS) ? p / J : 0;
+    const int gj = (weights == MVP_REFINE_W_GAUSS) ? (int)(p % J) : 0;
+    unsigned used = 0;
+#pragma unroll
+    for (int j = 0; j < NV; j++) {
+        const int col = ci.v[j];
+        const float x = kp[col], y = kp[V + col], c = kp[2 * V + col];
+        bool ok = ((allowed >> j) & 1u) && view_usable(x, y, c, min_conf);
+        double ox = (double)x, oy = (double)y, a = 1.0, b = 0.0, d = 1.0;
+        if (weights == MVP_REFINE_W_CONF) {
+            a = d = (double)c;
+        } else if (weights == MVP_REFINE_W_GAUSS) {
+            const double* __restrict__ gq = gauss + ((gt * V + col) * (int64_t)J + gj) * 6;
+            const double g0 = gq[0], g1 = gq[1], g2 = gq[2], g3 = gq[3], g4 = gq[4], g5 = gq[5];
+            const bool fin = isfinite(g0) && isfinite(g1) && isfinite(g2) && isfinite(g3) && isfinite(g4) && isfinite(g5);
+            const bool zero = g0 == 0 && g1 == 0 && g2 == 0 && g3 == 0 && g4 == 0 && g5 == 0;
+            const double sa = g2 + (double)cov_floor, sb = g3, sd = g5 + (double)cov_floor;
+            const double det = sa * sd - sb * sb;
+            ok = ok && fin && !zero && sa > 0 && det > 0;
+            const double idet = 1.0 / det;
+            ox = g0, oy = g1;
+            a = sd * idet, b = -sb * idet, d = sa * idet;
+        }
+        used |= (ok ? 1u : 0u) << j;
+        s_zx[j][tid] = ok ? ox : 0.0;
+        s_zy[j][tid] = ok ? oy : 0.0;
+        s_wxx[j][tid] = ok ? a : 0.0;
+        s_wxy[j][tid] = ok ? b : 0.0;
+        s_wyy[j][tid] = ok ? d : 0.0;
+    }
+    const float s0 = xyz0[3 * p + 0], s1 = xyz0[3 * p + 1], s2 = xyz0[3 * p + 2];
+    const double dinf = (double)INFINITY;
+    bool alive = __popc(used) >= 2 && isfinite(s0) && isfinite(s1) && isfinite(s2);
+    bool failed = !alive, conv = false, conv_step = false;
+    double X[3] = {(double)s0, (double)s1, (double)s2};
+    double delta[3] = {0.0, 0.0, 0.0};
+    double f = dinf, g[3] = {0, 0, 0}, H[6] = {0, 0, 0, 0, 0, 0};
+    double lambda = 1e-3;
+    int trials = 0;
+#pragma unroll 1
+    for (int it = 0;; it++) {
+        // trip 0: the seed itself (delta = 0); trip it > 0: trial `it`
+        const double Xn[3] = {X[0] + delta[0], X[1] + delta[1], X[2] + delta[2]};
+        double fn = 0, gn[3] = {0, 0, 0}, Hn[6] = {0, 0, 0, 0, 0, 0};
+        bool front = true;
+#pragma unroll 1
+        for (int j = 0; j < NV; j++) {
+            const RefineCam c = refine_cam(cams + ((cols >> (4 * j)) & 15u) * MVP_CAM_DOUBLES);
+            double fj = 0, gj3[3] = {0, 0, 0}, Hj[6] = {0, 0, 0, 0, 0, 0};
+            const bool infront = refine_view_terms(c, Xn, s_zx[j][tid], s_zy[j][tid], s_wxx[j][tid], s_wxy[j][tid],
+                                                   s_wyy[j][tid], fj, gj3, Hj);
+            const bool u = (used >> j) & 1u;
+            front = front && (infront || !u);
+            const bool add = u && infront;
+            fn += add ? fj : 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) gn[k] += add ? gj3[k] : 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; k++) Hn[k] += add ? Hj[k] : 0.0;
+        }
+        fn = front ? fn : dinf;
+        const bool fin = isfinite(fn);
+        bool accept;
+        if (it == 0) {
+            failed = failed || !fin;
+            alive = alive && fin;
+            accept = alive;
+        } else {
+            accept = alive && fin && fn <= f;
+            lambda = !alive ? lambda : (accept ? fmax(lambda * 0.1, 1e-12) : lambda * 10.0);
+            trials += alive ? 1 : 0;
+            conv = conv || (alive && conv_step);
+        }
+        f = accept ? fn : f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            X[k] = accept ? Xn[k] : X[k];
+            g[k] = accept ? gn[k] : g[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 6; k++) H[k] = accept ? Hn[k] : H[k];
+        alive = alive && !conv;
+        if (it >= max_iter) break;
+        if (__ballot(alive) == 0) break;
+        // propose: (H + lambda·diag H) delta = -g
+        const double damp = 1.0 + lambda;
+        const double A[6] = {H[0] * damp, H[1], H[2], H[3] * damp, H[4], H[5] * damp};
+        const double mg[3] = {-g[0], -g[1], -g[2]};
+        double L[6];
+        const bool pd = chol3(A, L);
+        chol3_solve(L, mg, delta);
+        failed = failed || (alive && !pd);
+        alive = alive && pd;
+#pragma unroll
+        for (int k = 0; k < 3; k++) delta[k] = alive ? delta[k] : 0.0;
+        const double dn = sqrt(delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2]);
+        const double xn = sqrt(X[0] * X[0] + X[1] * X[1] + X[2] * X[2]);
+        conv_step = dn <= tol * (xn + tol);
+    }
+    const float qnan = __builtin_nanf("");
+    float cov[6] = {qnan, qnan, qnan, qnan, qnan, qnan};
+    if (!failed) {
+        double L[6];
+        if (chol3(H, L)) {
+            // columns of H⁻¹
+            const double e0[3] = {1, 0, 0}, e1[3] = {0, 1, 0}, e2[3] = {0, 0, 1};
+            double c0[3], c1[3], c2[3];
+            chol3_solve(L, e0, c0);
+            chol3_solve(L, e1, c1);
+            chol3_solve(L, e2, c2);
+            cov[0] = (float)c0[0], cov[1] = (float)c0[1], cov[2] = (float)c0[2];
+            cov[3] = (float)c1[1], cov[4] = (float)c1[2], cov[5] = (float)c2[2];
+        }
+    }
+    out_xyz[3 * p + 0] = failed ? s0 : (float)X[0];
+    out_xyz[3 * p + 1] = failed ? s1 : (float)X[1];
+    out_xyz[3 * p + 2] = failed ? s2 : (float)X[2];
+    if (out_cov) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) out_cov[6 * p + k] = cov[k];
+    }
+    if (out_cost) out_cost[p] = failed ? qnan : (float)f;
+    if (out_status) out_status[p] = failed ? (uint8_t)0x80 : (uint8_t)(trials | (conv ? 0 : 0x40));
+}
+
+}  // namespace
+
+extern "C" int mvp_triangulate_refine(const float* kpts, int64_t n_points, int V, const double* cams, int n_cams,
+                                      const int* cam_idx, int n_cam_idx, const float* xyz0, const uint8_t* mask,
+                                      int weights, const double* gauss, int J, float min_conf, float cov_floor,
+                                      int max_iter, double tol, float* out_xyz, float* out_cov, float* out_cost,
+                                      uint8_t* out_status, void* stream) {
+    MVP_ABI_BEGIN
+    const char* fn = "mvp_triangulate_refine";
+    const CamIdx ci = tri_parse_args(fn, n_points, V, n_cams, cam_idx, n_cam_idx);
+    MVP_REQUIRE(weights >= MVP_REFINE_W_UNIT && weights <= MVP_REFINE_W_GAUSS,
+                "mvp_triangulate_refine: weights=%d (0..2)", weights);
+    if (weights == MVP_REFINE_W_GAUSS) {
+        MVP_REQUIRE(gauss != nullptr, "mvp_triangulate_refine: MVP_REFINE_W_GAUSS needs gauss_dev");
+        MVP_REQUIRE(J > 0 && n_points % J == 0, "mvp_triangulate_refine: J=%d (> 0, dividing n_points=%lld)", J,
+                    (long long)n_points);
+    }
+    MVP_REQUIRE(!std::isnan(min_conf), "mvp_triangulate_refine: min_conf is NaN");
+    MVP_REQUIRE(cov_floor >= 0.f, "mvp_triangulate_refine: cov_floor=%g (not NaN, >= 0)", (double)cov_floor);
+    MVP_REQUIRE(max_iter >= 0 && max_iter <= 63, "mvp_triangulate_refine: max_iter=%d (0..63)", max_iter);
+    MVP_REQUIRE(std::isfinite(tol) && tol > 0, "mvp_triangulate_refine: tol=%g (finite, > 0)", tol);
+    if (n_points == 0) return MVP_OK;
+    MVP_REQUIRE(kpts && cams && xyz0 && out_xyz, "mvp_triangulate_refine: null device pointer");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid(tri_grid(fn, n_points)), block(kBlock);
+    tri_dispatch_views(n_cam_idx, [&](auto nv) {
+        hipLaunchKernelGGL((triangulate_refine_kernel<decltype(nv)::value>), grid, block, 0, s, kpts, n_points, V, cams,
+                           ci, xyz0, mask, weights, gauss, J, min_conf, cov_floor, max_iter, tol, out_xyz, out_cov,
+                           out_cost, out_status);
+    });
+    MVP_HIP(hipGetLastError());
+    MVP_ABI_END
+}

@@ -19,7 +19,7 @@ CAM_DOUBLES = 40
 TRI_REFERENCE = 0
 TRI_ALL_VIEWS = 1
 TRI_EXACT_JACOBI = 0x10  # mode flag: exact Jacobi SVD for every point (mvpose.h)
-TRI_TOLERANCE = 0x20     # mode flag: throughput solver validated to <= 1e-4 world units (mvpose.h)
+TRI_TOLERANCE = 0x20     # mode flag: throughput solver, certified bit-identical to the exact path (mvpose.h)
 TRI_ROBUST = 2           # Python-level only (MultiViewPipeline mode): triangulate_robust, never an mvp_triangulate mode
 REFINE_W_UNIT = 0        # mvp_triangulate_refine weights (mvpose.h MVP_REFINE_W_*)
 REFINE_W_CONF = 1
@@ -44,6 +44,34 @@ def _require(t: torch.Tensor, dtype, name: str):
         raise ValueError(f"{name} must live on the GPU (no CPU fallback)")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
+
+
+def _tri_args(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int]):
+    """The triangulation fronts' shared checks: kpts (..., 3, V) float32 and cams (n_cams, 40)
+    float64, both on the GPU.  Returns V, the leading shape, its number of points and cam_idx as
+    a ctypes int array."""
+    _require(kpts, torch.float32, "kpts")
+    _require(cams, torch.float64, "cams")
+    if kpts.dim() < 2 or kpts.shape[-2] != 3:
+        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
+    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
+        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
+    lead = tuple(kpts.shape[:-2])
+    n = int(np.prod(lead)) if lead else 1
+    ci = (ctypes.c_int * len(cam_idx))(*[int(c) for c in cam_idx])
+    return kpts.shape[-1], lead, n, ci
+
+
+def _pack_view_bits(mask: torch.Tensor) -> torch.Tensor:
+    """(..., NV) bool -> (...) uint8 with bit i set for view i: the kernels' per-point view mask."""
+    place = torch.tensor([1 << i for i in range(mask.shape[-1])], dtype=torch.int32, device=mask.device)
+    return (mask.to(torch.int32) * place).sum(-1).to(torch.uint8).contiguous()
+
+
+def _unpack_view_bits(bits: torch.Tensor, nv: int) -> torch.Tensor:
+    """_pack_view_bits' inverse: (...) uint8 -> (..., nv) bool."""
+    shifts = torch.arange(nv, dtype=torch.uint8, device=bits.device)
+    return ((bits.unsqueeze(-1) >> shifts) & 1).to(torch.bool)
 
 
 def pack_camera(K, R, T, dist) -> np.ndarray:
@@ -101,15 +129,7 @@ def triangulate(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int] =
         mode = int(mode) | TRI_EXACT_JACOBI
     if tolerance:
         mode = int(mode) | TRI_TOLERANCE
-    _require(kpts, torch.float32, "kpts")
-    _require(cams, torch.float64, "cams")
-    if kpts.dim() < 2 or kpts.shape[-2] != 3:
-        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
-    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
-        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
-    V = kpts.shape[-1]
-    lead = tuple(kpts.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
     if out is None:
         out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
     else:
@@ -117,8 +137,7 @@ def triangulate(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int] =
         if tuple(out.shape) != lead + (3,):
             raise ValueError("out has the wrong shape")
     xyzw = torch.empty(lead + (4,), dtype=torch.float64, device=kpts.device) if return_xyzw else None
-    ci = (ctypes.c_int * len(cam_idx))(*[int(c) for c in cam_idx])
-    call("mvp_triangulate", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, len(cam_idx), int(mode),
+    call("mvp_triangulate", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, len(ci), int(mode),
          _ptr(out), _ptr(xyzw) if xyzw is not None else None, _stream(kpts.device))
     return (out, xyzw) if return_xyzw else out
 
@@ -135,25 +154,14 @@ def triangulate_robust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     views; NaN where fewer than two views agree within inlier_px), the views used, and every
     valid view's reprojection error in undistorted pixels against the returned point (+inf
     behind the camera, NaN for views that are not finite or below min_conf)."""
-    _require(kpts, torch.float32, "kpts")
-    _require(cams, torch.float64, "cams")
-    if kpts.dim() < 2 or kpts.shape[-2] != 3:
-        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
-    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
-        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
-    V = kpts.shape[-1]
-    lead = tuple(kpts.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
-    nv = len(cam_idx)
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
+    nv = len(ci)
     out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
     bits = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
     err = torch.empty(lead + (nv,), dtype=torch.float32, device=kpts.device) if return_err else None
-    ci = (ctypes.c_int * nv)(*[int(c) for c in cam_idx])
     call("mvp_triangulate_robust", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
          float(min_conf), _ptr(out), _ptr(bits), _ptr(err) if err is not None else None, _stream(kpts.device))
-    shifts = torch.arange(nv, dtype=torch.uint8, device=kpts.device)
-    inliers = ((bits.unsqueeze(-1) >> shifts) & 1).to(torch.bool)
-    return out, inliers, err
+    return out, _unpack_view_bits(bits, nv), err
 
 
 def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz0: torch.Tensor, *,
@@ -176,17 +184,9 @@ def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     and in the covariance."""
     if weights not in REFINE_WEIGHTS:
         raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
-    _require(kpts, torch.float32, "kpts")
-    _require(cams, torch.float64, "cams")
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
     _require(xyz0, torch.float32, "xyz0")
-    if kpts.dim() < 2 or kpts.shape[-2] != 3:
-        raise ValueError(f"kpts must be (..., 3, V), got {tuple(kpts.shape)}")
-    if cams.dim() != 2 or cams.shape[1] != CAM_DOUBLES:
-        raise ValueError(f"cams must be (n_cams, {CAM_DOUBLES}), got {tuple(cams.shape)}")
-    V = kpts.shape[-1]
-    lead = tuple(kpts.shape[:-2])
-    n = int(np.prod(lead)) if lead else 1
-    nv = len(cam_idx)
+    nv = len(ci)
     if tuple(xyz0.shape) != lead + (3,):
         raise ValueError(f"xyz0 must be {lead + (3,)}, got {tuple(xyz0.shape)}")
     J = 0
@@ -203,13 +203,11 @@ def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
         _require(mask, torch.bool, "mask")
         if tuple(mask.shape) != lead + (nv,):
             raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
-        place = torch.tensor([1 << i for i in range(nv)], dtype=torch.int32, device=kpts.device)
-        bits = (mask.to(torch.int32) * place).sum(-1).to(torch.uint8).contiguous()
+        bits = _pack_view_bits(mask)
     out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
     cov6 = torch.empty(lead + (6,), dtype=torch.float32, device=kpts.device)
     cost = torch.empty(lead, dtype=torch.float32, device=kpts.device)
     status = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
-    ci = (ctypes.c_int * nv)(*[int(c) for c in cam_idx])
     call("mvp_triangulate_refine", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
          _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
          _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor), int(max_iter),

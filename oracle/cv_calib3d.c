@@ -103,7 +103,7 @@ void orc_undistort_points_f64(const double* src, int64_t n, const double* K, con
 
 /* ---- glibc 2.35 __ieee754_hypot restated (sysdeps/ieee754/dbl-64/e_hypot.c, non-FMA kernel) ---
  * The oracle's Jacobi calls libm's hypot, as OpenCV's does; this restatement is the text the
- * device's exact path (csrc/triangulate.hip hypot_glibc) follows, checked against libm by
+ * device's exact path (csrc/tri_common.h hypot_glibc) follows, checked against libm by
  * tests/test_oracle_triangulate.py. */
 static double orc_hypot_kernel(double ax, double ay)
 {

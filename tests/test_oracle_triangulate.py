@@ -68,7 +68,7 @@ def test_all_views_extension_consistent():
 
 def test_hypot_restatement_matches_libm():
     """OpenCV's JacobiSVDImpl_ calls std::hypot = libm's (glibc 2.35 on this image and the GPU
-    box).  The device's exact path restates glibc's algorithm (csrc/triangulate.hip hypot_glibc);
+    box).  The device's exact path restates glibc's algorithm (csrc/tri_common.h hypot_glibc);
     the same text in C must equal libm on random pairs incl. near-equal magnitudes, wide exponent
     ranges, zeros and the rotation angles' typical (2p, a - b) pairs."""
     rng = np.random.default_rng(3)

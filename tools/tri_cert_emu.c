@@ -1,5 +1,5 @@
-/* CPU emulation of the certified tolerance triangulation (csrc/triangulate.hip
- * undistort_pair_tol / normal_eq_null_vector / null_vector_delta2) against the oracle's exact
+/* CPU emulation of the certified tolerance triangulation (csrc/triangulate_tol.hip
+ * undistort_pair_tol / normal_eq_null_vector, csrc/tri_common.h null_vector_delta2) against the oracle's exact
  * path: counts points whose f32 outputs would differ (must all be caught) and the fallback rate.
  * Build: gcc -O2 -ffp-contract=off tools/tri_cert_emu.c -o /tmp/tri_cert_emu -lm
  * Input: python tools/tri_cert_sets.py (writes /tmp/tri/sets.bin).  Usage: tri_cert_emu [NF32] */
