@@ -539,6 +539,60 @@ int mvp_linear_interpolation(const float* pts_dev, int T, int P, int D, int k, f
                              void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Covariance-weighted trajectory smoothing with gap filling (no reference counterpart; the
+ * smoothness prior is the reference's second-difference cost, pose_refinement.py:836-845, the
+ * likelihood is mvp_triangulate_refine's covariance).
+ *
+ * Chains are independent.  Chain p has unknowns X_t in R³, t = 0..T-1.  Frame (t, p) is
+ * OBSERVED when all of these hold:
+ *   - its three input coordinates are finite;
+ *   - valid[t][p] != 0, where valid is given;
+ *   - where cov is given: its six numbers (xx, xy, xz, yy, yz, zz) are finite and
+ *     S = cov + cov_floor·I is positive definite (all three Cholesky pivots > 0).
+ * An observed frame has W_t = S⁻¹ (W_t = I / sigma0² without cov); an unobserved frame has
+ * W_t = 0 and its input coordinates are never used.  The output minimises
+ *
+ *   E(X) = ½ Σ_t (X_t − z_t)ᵀ W_t (X_t − z_t) + ½ λ Σ_{t=2}^{T−1} |X_t − 2 X_{t−1} + X_{t−2}|²
+ *
+ * i.e. solves (blockdiag(W) + λ·(D₂ᵀD₂ ⊗ I₃)) X = blockdiag(W) z, D₂ the (T−2)×T second-
+ * difference matrix: symmetric, block-pentadiagonal in 3x3 blocks, positive definite whenever the
+ * chain has >= 2 observed frames.  Consequences: gaps are filled by the cubic-spline-like
+ * interpolant; before the first and after the last observed frame the track continues as a
+ * straight line; T = 2 with both frames observed returns the inputs; data exactly affine in t are
+ * returned unchanged for every λ.  λ = 1/σ_a², σ_a the standard deviation of a joint's second
+ * difference per frame.
+ *
+ * Everything is fp64 on the device from the float32 inputs; FMA contraction is allowed, so the
+ * results carry no bit-exactness contract (as for mvp_triangulate_refine).
+ *
+ * Failure: a chain fails when it has fewer than 2 observed frames or when any pivot of the
+ * factorisation is not > 0.  A failed chain returns its input bits as out_xyz (NaNs included),
+ * NaN residuals and status 0x80: a smoothed chain is never less defined than its input.
+ *
+ * The solve is parallel in time by the partition method: chunks of `chunk` interior frames with
+ * 2-frame separators between them, one lane per (chain, chunk), then one reduced block-
+ * tridiagonal system per chain on the separators (csrc/smooth.hip).  chunk = 0 picks the length
+ * automatically; otherwise 4 <= chunk <= 4096.  The result does not depend on chunk beyond fp64
+ * rounding.
+ *
+ * mvp_trajectory_smooth_plan : what a call with (T, P, chunk) will use: the chunk length, the
+ *   number of chunks per chain and the workspace size in bytes (any of the three may be NULL).
+ * mvp_trajectory_smooth : xyz_dev [T][P][3] f32; cov_dev [T][P][6] f32 or NULL; valid_dev [T][P]
+ *   uint8 or NULL; workspace_dev >= the plan's bytes, owned by the caller (its contents are
+ *   scratch).  out_xyz_dev [T][P][3] f32 (must not be xyz_dev); out_resid_dev [T][P] f32 or NULL =
+ *   (X_t − z_t)ᵀ W_t (X_t − z_t), the squared Mahalanobis distance of the fp64 solution before it
+ *   is rounded, NaN for unobserved frames and failed chains; out_observed_dev [T][P] uint8 (1/0)
+ *   or NULL; out_status_dev [P] uint8 (0 or 0x80) or NULL.  Requires T >= 1, P >= 1,
+ *   lambda_smooth and sigma0 finite and > 0, cov_floor >= 0.  Stream-ordered: no host
+ *   synchronisation and no allocation inside the call.
+ * ------------------------------------------------------------------------- */
+int mvp_trajectory_smooth_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_trajectory_smooth(const float* xyz_dev, const float* cov_dev, const uint8_t* valid_dev, int T, int P,
+                          double lambda_smooth, float sigma0, float cov_floor, int chunk, void* workspace_dev,
+                          int64_t workspace_bytes, float* out_xyz_dev, float* out_resid_dev,
+                          uint8_t* out_observed_dev, uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's
  * recordings (utils.py:849-909 read_video_as_frames; synchronize_videos.py:64,240 writes them with
  * cv2.VideoWriter_fourcc(*'mp4v')).  Simple Profile: I / P-VOPs, video packets, H.263 or MPEG

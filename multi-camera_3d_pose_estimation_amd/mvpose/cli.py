@@ -10,7 +10,9 @@
 * ``pose_refinement`` (pose_refinement.py:1099-1255): missing arguments filled
   from recording_log.yaml; ``linear_interpolation`` always runs (GPU kernel) and
   is saved when requested; ``SGD`` runs the one-launch GPU refinement with the
-  ``SGD`` section of --refinement_params_yaml and saves ``kpts_3d_SGD.npy``.
+  ``SGD`` section of --refinement_params_yaml and saves ``kpts_3d_SGD.npy``;
+  ``smooth`` (no reference counterpart) runs the covariance-weighted smoother with the
+  ``smooth`` section and saves ``kpts_3d_smooth.npy`` and ``kpts_3d_smooth_resid.npy``.
 """
 from __future__ import annotations
 
@@ -155,8 +157,10 @@ def record_and_estimate_pose_main(argv=None):
 
 
 # --------------------------------------------------------------------- refinement
-def pose_refinement_parser():
-    """Flags of pose_refinement.py:1100-1116."""
+def pose_refinement_parser(extensions=False):
+    """Flags of pose_refinement.py:1100-1116; extensions=True (what the command line uses) adds
+    the flags beyond the reference's: --kpts_3d_cov, --kpts_3d_refine_status (inputs of the
+    "smooth" refinement type)."""
     p = argparse.ArgumentParser()
     p.add_argument("--run_path", type=str)
     p.add_argument("--refinement_types", nargs="+", default=["linear_interpolation"])
@@ -173,6 +177,9 @@ def pose_refinement_parser():
     p.add_argument("--body_part_lengths_individual_name_yaml", default="my_lengths", type=str)
     p.add_argument("--ignore_body_lengths", action="store_true")
     p.add_argument("--interpolate_before_SGD", action="store_true")
+    if extensions:   # what record_and_estimate_pose --refine writes beside kpts_3d.npy
+        p.add_argument("--kpts_3d_cov", type=str)
+        p.add_argument("--kpts_3d_refine_status", type=str)
     return p
 
 
@@ -181,8 +188,8 @@ def _load_if_exists(path):
 
 
 def pose_refinement_main(argv=None):
-    from .refine import Optimized_3d_Pose_Estimation, linear_interpolation
-    args = pose_refinement_parser().parse_args(argv)
+    from .refine import Optimized_3d_Pose_Estimation, linear_interpolation, smooth_trajectory
+    args = pose_refinement_parser(extensions=True).parse_args(argv)
     if args.run_path is None:
         args.run_path = os.getcwd()
     if args.save_path is None:
@@ -236,6 +243,18 @@ def pose_refinement_main(argv=None):
         np.save(path, best.numpy() if best is not None else np.array(None))
         outputs["SGD"] = path
         types.discard("SGD")
+    if "smooth" in types:   # whole-recording smoother; sigma0 stands in where no covariance file exists
+        kw = prepare_kwargs(smooth_trajectory, params.get("smooth"))
+        kw.update({"cov": _load_if_exists(args.kpts_3d_cov), "status": _load_if_exists(args.kpts_3d_refine_status),
+                   "return_info": True})
+        smooth, info = smooth_trajectory(kpts_3d, **kw)
+        path = os.path.join(args.save_path, "kpts_3d_smooth.npy")
+        print(f"saving smoothed trajectory at {path}")
+        np.save(path, smooth)
+        np.save(os.path.join(args.save_path, "kpts_3d_smooth_resid.npy"), info["resid"])
+        outputs["smooth"] = path
+        types.discard("smooth")
     if types:
-        raise ValueError(f"unknown refinement type(s) {sorted(types)}; expected linear_interpolation and/or SGD")
+        raise ValueError(f"unknown refinement type(s) {sorted(types)}; expected linear_interpolation, SGD "
+                         "and/or smooth")
     return outputs

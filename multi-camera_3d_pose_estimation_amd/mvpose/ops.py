@@ -242,3 +242,64 @@ def triangulate_points_f64(kpts: torch.Tensor, cams: torch.Tensor, return_xyzw: 
     call("mvp_triangulate_points_f64", _ptr(kpts), n, _ptr(cams), _ptr(out),
          _ptr(xyzw) if xyzw is not None else None, _stream(kpts.device))
     return (out, xyzw) if return_xyzw else out
+
+
+def trajectory_smooth_plan(T: int, P: int, chunk: int = 0):
+    """What trajectory_smooth will use for (T, P, chunk) (mvp_trajectory_smooth_plan): the chunk
+    length, the chunks per chain and the workspace bytes."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_trajectory_smooth_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
+         ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
+def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid: torch.Tensor | None = None, *,
+                      lambda_smooth: float = 1.0, sigma0: float = 1.0, cov_floor: float = 0.0, chunk: int = 0,
+                      want_resid: bool = True, want_observed: bool = True, want_status: bool = True):
+    """Covariance-weighted trajectory smoothing with gap filling (mvp_trajectory_smooth; the
+    problem is stated in include/mvpose.h; no reference counterpart).
+
+    xyz (T, P, 3) float32 on the GPU; cov (T, P, 3, 3) or (T, P, 6) float32 (the upper triangle
+    xx, xy, xz, yy, yz, zz is the one read) or None (every observed frame then weighs
+    I / sigma0²); valid (T, P) bool or uint8 or None.  Per chain p the minimiser of
+    ½ Σ (X_t − z_t)ᵀ W_t (X_t − z_t) + ½ lambda_smooth Σ |X_t − 2 X_{t−1} + X_{t−2}|² with
+    W_t = (cov_t + cov_floor·I)⁻¹ on observed frames and 0 elsewhere: gaps are filled, the ends
+    continue as straight lines.  chunk: frames per lane of the time-parallel solve, 0 = automatic.
+    Returns (xyz (T, P, 3) float32, resid (T, P) float32 squared Mahalanobis distance of each
+    observed frame to the smooth track (NaN elsewhere), observed (T, P) bool, status (P,) uint8:
+    0, or 0x80 for a chain with fewer than 2 observed frames, which returns its input).  An
+    output switched off by its want_* flag comes back as None.  The workspace is a torch.empty on
+    the call's stream, sized by trajectory_smooth_plan."""
+    _require(xyz, torch.float32, "xyz")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (T, P, 3), got {tuple(xyz.shape)}")
+    T, P = int(xyz.shape[0]), int(xyz.shape[1])
+    cov6 = None
+    if cov is not None:
+        if not isinstance(cov, torch.Tensor) or cov.dtype != torch.float32 or not cov.is_cuda:
+            raise TypeError("cov must be a float32 torch.Tensor on the GPU")
+        if tuple(cov.shape) == (T, P, 3, 3):
+            cov6 = cov.reshape(T, P, 9)[..., [0, 1, 2, 4, 5, 8]].contiguous()
+        elif tuple(cov.shape) == (T, P, 6):
+            cov6 = cov.contiguous()
+        else:
+            raise ValueError(f"cov must be {(T, P, 3, 3)} or {(T, P, 6)}, got {tuple(cov.shape)}")
+    v8 = None
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or not valid.is_cuda:
+            raise TypeError("valid must be a bool or uint8 torch.Tensor on the GPU")
+        if tuple(valid.shape) != (T, P):
+            raise ValueError(f"valid must be {(T, P)}, got {tuple(valid.shape)}")
+        v8 = valid.to(torch.uint8).contiguous()
+    _, _, nbytes = trajectory_smooth_plan(T, P, chunk)
+    dev = xyz.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty_like(xyz)
+    resid = torch.empty((T, P), dtype=torch.float32, device=dev) if want_resid else None
+    observed = torch.empty((T, P), dtype=torch.uint8, device=dev) if want_observed else None
+    status = torch.empty((P,), dtype=torch.uint8, device=dev) if want_status else None
+    opt = (lambda t: _ptr(t) if t is not None else None)
+    call("mvp_trajectory_smooth", _ptr(xyz), opt(cov6), opt(v8), T, P, float(lambda_smooth), float(sigma0),
+         float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(resid), opt(observed), opt(status),
+         _stream(dev))
+    return out, resid, observed.to(torch.bool) if observed is not None else None, status

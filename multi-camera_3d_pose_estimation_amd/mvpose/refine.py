@@ -11,6 +11,8 @@ Host mirror of the reference's refinement API (pose_refinement.py):
 * ``refine_trajectories(...)``: M independent trajectories (same rig) in one
   launch, one workgroup each — the throughput form (SGD shards as replicas).
 * ``project_points_torch`` (:94-179) and ``linear_interpolation`` (:15-84) on the GPU.
+* ``smooth_trajectory`` (no reference counterpart): covariance-weighted smoothing of a whole
+  recording with gap filling, a direct solve on the GPU (mvp_trajectory_smooth).
 
 * Extrinsic learning from samples (``sgd_optimize(extrinsic_optimization_IDs=[id],
   optimize_trajectory=False, GT_camera_IDs=[a, b])``, :684-706, :800-831, :915-943):
@@ -214,6 +216,92 @@ def linear_interpolation(points, k=5, k_std=2, median_std=2, use_rolling_average
          int(bool(use_rolling_average)), int(bool(filter_distance_from_median)), _ptr(out), _stream(dev))
     out = out[..., 0] if squeeze else out
     return out.to(home) if was_tensor else out.cpu().numpy()
+
+
+def gap_mask(observed, max_gap):
+    """(T, P) bool: frames inside a run of unobserved frames longer than max_gap (leading and
+    trailing runs count).  observed (T, P) bool tensor."""
+    T = observed.shape[0]
+    idx = torch.arange(T, device=observed.device).unsqueeze(1).expand_as(observed)
+    last = torch.where(observed, idx, torch.full_like(idx, -1)).cummax(0).values
+    nxt = torch.where(observed, idx, torch.full_like(idx, T)).flip(0).cummin(0).values.flip(0)
+    return ~observed & ((nxt - last - 1) > int(max_gap))
+
+
+def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1.0, cov_floor=0.0, robust_k=None,
+                      robust_iters=3, max_gap=None, return_info=False, device=None):
+    """Covariance-weighted smoothing of a whole recording with gap filling (mvp_trajectory_smooth,
+    stated in include/mvpose.h; no reference counterpart).  points (T, P, 3); cov (T, P, 3, 3) or
+    (T, P, 6), e.g. kpts_3d_cov.npy, or None (every frame then has covariance sigma0²·I); status
+    (T, P) uint8, mvp_triangulate_refine's status: frames with bit 0x80 set are not valid.
+    Returns float32 (T, P, 3) (numpy in, numpy out; tensors stay tensors): per joint the
+    minimiser of the Gaussian likelihood of the points plus lambda_smooth times the squared
+    second differences.  Frames with NaN points, NaN or indefinite covariance or a failed status
+    are filled in from their neighbours; a joint with fewer than 2 usable frames is returned as
+    it came.
+
+    lambda_smooth = 1 / σ_a², σ_a the standard deviation of a joint's second difference per frame
+    in the points' units: the default 1.0 says about 1 unit per frame², i.e. with centimetres at
+    30 fps about 10 m/s².  It is a documented default, not a tuned one.
+
+    robust_k: Huber reweighting when not None.  After a solve d_t = sqrt(resid_t) is taken
+    against the original weights, each observed frame's original covariance (cov + cov_floor·I
+    rounded to float32, or sigma0²·I) is scaled by max(1, d_t / robust_k) and the solve repeated,
+    robust_iters times after the first; resid is then the one against the original weights.
+    max_gap: frames inside a run of unobserved frames longer than max_gap (leading and trailing
+    runs count) are returned as NaN; the solve itself is unchanged.  None = no limit.
+    return_info=True returns (points, {"resid" (T, P) float32, "observed" (T, P) bool, "status"
+    (P,) uint8})."""
+    was_tensor = isinstance(points, torch.Tensor)
+    x = points if was_tensor else torch.from_numpy(np.ascontiguousarray(np.asarray(points)))
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError("points must be (time, n_points, 3)")
+    home = x.device
+    dev = _device(device if device is not None else (home if home.type == "cuda" else "cuda"))
+    x = x.to(device=dev, dtype=torch.float32).contiguous()
+    T, P = x.shape[:2]
+    c6 = None
+    if cov is not None:
+        c = torch.as_tensor(cov).to(device=dev, dtype=torch.float32)
+        if tuple(c.shape) == (T, P, 3, 3):
+            c = c.reshape(T, P, 9)[..., [0, 1, 2, 4, 5, 8]]
+        if tuple(c.shape) != (T, P, 6):
+            raise ValueError(f"cov must be {(T, P, 3, 3)} or {(T, P, 6)}, got {tuple(torch.as_tensor(cov).shape)}")
+        c6 = c.contiguous()
+    valid = None
+    if status is not None:
+        st = torch.as_tensor(status).to(dev)
+        if tuple(st.shape) != (T, P):
+            raise ValueError(f"status must be {(T, P)}, got {tuple(st.shape)}")
+        valid = (st.to(torch.int32) & 0x80) == 0
+    kw = dict(lambda_smooth=lambda_smooth, sigma0=sigma0)
+    diag = torch.tensor([1, 0, 0, 1, 0, 1], dtype=torch.float32, device=dev)
+    if robust_k is None:
+        out, resid, observed, st_out = ops.trajectory_smooth(x, c6, valid, cov_floor=cov_floor, **kw)
+    else:
+        if c6 is not None:   # the covariance the loop scales: cov + cov_floor·I, float32
+            base = c6 + torch.tensor(float(cov_floor), dtype=torch.float32, device=dev) * diag
+            out, resid, observed, st_out = ops.trajectory_smooth(x, base, valid, cov_floor=0.0, **kw)
+        else:
+            s2 = torch.tensor(float(sigma0), dtype=torch.float32, device=dev) ** 2
+            base = (s2 * diag).expand(T, P, 6)
+            out, resid, observed, st_out = ops.trajectory_smooth(x, None, valid, cov_floor=0.0, **kw)
+        scale = torch.ones((T, P), dtype=torch.float32, device=dev)
+        k = torch.tensor(float(robust_k), dtype=torch.float32, device=dev)
+        for _ in range(int(robust_iters)):
+            d = torch.sqrt(resid * scale)
+            scale = torch.where(d > k, d / k, torch.ones_like(d))     # NaN (unobserved) -> 1
+            out, resid, observed, st_out = ops.trajectory_smooth(x, (base * scale.unsqueeze(-1)).contiguous(), valid,
+                                                                 cov_floor=0.0, **kw)
+        resid = resid * scale
+    if max_gap is not None:
+        out = torch.where(gap_mask(observed, max_gap).unsqueeze(-1), torch.full_like(out, float("nan")), out)
+    if was_tensor:
+        res, info = out.to(home), {"resid": resid.to(home), "observed": observed.to(home), "status": st_out.to(home)}
+    else:
+        res = out.cpu().numpy()
+        info = {"resid": resid.cpu().numpy(), "observed": observed.cpu().numpy(), "status": st_out.cpu().numpy()}
+    return (res, info) if return_info else res
 
 
 EXT_SUMS = 14
