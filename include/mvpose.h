@@ -593,6 +593,54 @@ int mvp_trajectory_smooth(const float* xyz_dev, const float* cov_dev, const uint
                           uint8_t* out_observed_dev, uint8_t* out_status_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Epipolar lag-cost scan: the data term of pose-based frame synchronisation (no reference
+ * counterpart; the reference synchronises by hand, synchronize_videos.py).  For a calibrated pair
+ * of cameras, keypoints of the same joint satisfy the epipolar constraint only when their frames
+ * show the same instant; the scan scores that constraint for every pair of listed views and every
+ * frame lag.
+ *
+ * kpts_dev [T][J][3][V] float32 (the kpts_2d layout; rows x, y, confidence), cams_dev,
+ * cam_idx_host / n_cam_idx = nv as for mvp_triangulate_robust: view i reads column cam_idx[i] and
+ * the parameters of camera cam_idx[i]; 2 <= nv <= 8.
+ *   Pairs: (a, b), a < b positions in cam_idx, in lexicographic order: NP = nv·(nv−1)/2, pair 0 =
+ *     (0, 1), pair 1 = (0, 2), ...
+ *   Usable keypoint: x and y finite, conf not NaN and conf >= min_conf (the rule of
+ *     mvp_triangulate_robust).  Its ideal pixel (u, v) is the float32 undistorted pixel the
+ *     triangulators use (OpenCV 4.9 undistortPoints restated: 5 iterations in fp64, P = K,
+ *     rounded to float32); x = (u, v, 1) in fp64.
+ *   Fundamental matrix, fp64, from the records of cameras cam_idx[a], cam_idx[b]:
+ *     F_ab = K_b⁻ᵀ [t]ₓ R K_a⁻¹ with R = R_b R_aᵀ, t = T_b − R T_a ([t]ₓ the cross-product
+ *     matrix), so that x_bᵀ F_ab x_a = 0 for noise-free matches.  The distance below does not
+ *     depend on the scale of F.
+ *   Cost: for every lag l in [−L, L], L = max_lag, every frame t with 0 <= t < T and
+ *     0 <= t + l < T and every joint j whose keypoint is usable in view a at frame t and in view b
+ *     at frame t + l, the squared Sampson distance of x_a = x(a, t, j) and x_b = x(b, t + l, j):
+ *       d² = (x_bᵀ F x_a)² / ((F x_a)₀² + (F x_a)₁² + (Fᵀ x_b)₀² + (Fᵀ x_b)₁²)
+ *     A term whose denominator is 0 or whose d² is not finite is skipped.
+ *       sum[p][l + L] = Σ min(d², trunc_px²)   (float64)
+ *       cnt[p][l + L] = number of terms         (int64)
+ *     The truncated quadratic is continuous in d², so rounding cannot move a term across the
+ *     threshold by more than its own rounding error.
+ * Arithmetic is fp64 (x_bᵀ F x_a cancels to ~1e-6 of its terms at 1 000-pixel coordinates); FMA
+ * contraction is allowed, so sum carries no bit contract against another implementation, but the
+ * same inputs give the same bits on every call: no floating-point atomics, a block-level
+ * reduction and a fixed-order final pass.
+ *
+ * mvp_epipolar_lag_cost_plan : what a call with (T, J, n_cam_idx, max_lag) will use: the time
+ *   tile in frames (a workgroup scores one tile of view a against all lags, csrc/sync.hip) and
+ *   the workspace size in bytes (either may be NULL).
+ * mvp_epipolar_lag_cost : workspace_dev >= the plan's bytes, owned by the caller (its contents
+ *   are scratch); out_sum_dev [NP][2L+1] float64, out_cnt_dev [NP][2L+1] int64.  Requires T >= 1,
+ *   1 <= J <= 1024, T·J < 2^31, 0 <= max_lag < T, min_conf not NaN, trunc_px finite and > 0.
+ *   Stream-ordered: no host synchronisation and no allocation inside the call.
+ * ------------------------------------------------------------------------- */
+int mvp_epipolar_lag_cost_plan(int T, int J, int n_cam_idx, int max_lag, int* tile_out, int64_t* workspace_bytes);
+int mvp_epipolar_lag_cost(const float* kpts_dev, int T, int J, int V, const double* cams_dev, int n_cams,
+                          const int* cam_idx_host, int n_cam_idx, int max_lag, float min_conf, float trunc_px,
+                          void* workspace_dev, int64_t workspace_bytes, double* out_sum_dev, int64_t* out_cnt_dev,
+                          void* stream);
+
+/* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's
  * recordings (utils.py:849-909 read_video_as_frames; synchronize_videos.py:64,240 writes them with
  * cv2.VideoWriter_fourcc(*'mp4v')).  Simple Profile: I / P-VOPs, video packets, H.263 or MPEG

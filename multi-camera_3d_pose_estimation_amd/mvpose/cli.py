@@ -57,7 +57,7 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                              checkerboard_display_parameter_yaml="./checkerboard_display_parameters.yaml",
                              origin_camera_idx=0, script_path=None, project_dir="", recording_length_seconds=10,
                              keep_unsynced_files=False, triangulation="reference", inlier_px=10.0,
-                             min_confidence=0.0, refine=None, cov_floor=1.0):
+                             min_confidence=0.0, refine=None, cov_floor=1.0, sync_from_pose=False, max_lag=60):
     """triangulation / inlier_px / min_confidence (no reference counterpart): "reference" (default)
     triangulates from cameras [0, 1] and writes exactly the reference's files; "all_views" and
     "robust" use every camera in camera_names (estimate_pose_from_video), record the three
@@ -66,7 +66,12 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
     refine / cov_floor (no reference counterpart): "unit", "conf" or "heatmap" refines the
     triangulated points by maximum likelihood (get_pose_3D); kpts_3d.npy then holds the refined
     points, and kpts_3d_seed.npy, kpts_3d_cov.npy (T,17,3,3) f32 and kpts_3d_refine_status.npy
-    (T,17) uint8 are written too, the two settings recorded in recording_log.yaml."""
+    (T,17) uint8 are written too, the two settings recorded in recording_log.yaml.
+    sync_from_pose / max_lag (no reference counterpart): the cameras' frame offsets are estimated
+    from the 2D keypoints over lags of -max_lag..max_lag frames (estimate_pose_from_video's
+    sync="pose"); kpts_2d.npy, heatmaps_2d.npy and everything after them then hold the frames cut
+    to the common instants, frame_offsets.npy (V,) int64 is written too, and recording_log.yaml
+    records the offsets, max_lag and the rejected pairs under "sync"."""
     if refine not in (None, "unit", "conf", "heatmap"):
         raise ValueError(f"refine {refine!r}: None, 'unit', 'conf' or 'heatmap'")
     from .pose_estimation import estimate_pose_from_video
@@ -80,7 +85,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
         raise NotImplementedError("webcam recording is outside the GPU hot path: pass --recording_paths")
     if synchronize_video:
         raise NotImplementedError("audio-based video synchronisation is outside the GPU hot path: pass "
-                                  "already synchronised recordings (omit --synchronize_video)")
+                                  "already synchronised recordings (omit --synchronize_video), or let --sync_from_pose "
+                                  "estimate the cameras' frame offsets from the 2D keypoints")
     recordings_folder = os.path.dirname(recording_paths[0])
     robust_kw = {}
     if triangulation != "reference":
@@ -88,6 +94,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                      "return_info": True}
     if refine is not None:
         robust_kw.update({"refine": refine, "cov_floor": cov_floor, "return_info": True})
+    if sync_from_pose:
+        robust_kw.update({"sync": "pose", "max_lag": max_lag, "return_info": True})
     kpts_2d, heatmaps, kpts_3d, *info = estimate_pose_from_video(
         camera_names, recording_paths, estimator_model, detector_model=detector_model, model_yaml=model_yaml,
         start_end_frames=[0, -1], confidence=0,
@@ -110,6 +118,14 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
         for key, name in (("seed", "kpts_3d_seed"), ("cov", "kpts_3d_cov"), ("refine_status", "kpts_3d_refine_status")):
             log[name] = str(os.path.join(recordings_folder, name + ".npy"))
             extra[name] = info[0][key]
+    if sync_from_pose:
+        pair_info = info[0]["sync_pairs"]
+        log["frame_offsets"] = str(os.path.join(recordings_folder, "frame_offsets.npy"))
+        extra["frame_offsets"] = info[0]["frame_offsets"]
+        log["sync"] = {"method": "pose", "max_lag": int(max_lag),
+                       "offsets": [int(o) for o in info[0]["frame_offsets"]],
+                       "rejected_pairs": [[camera_names[a], camera_names[b], r]
+                                          for (a, b), r in zip(pair_info["pairs"], pair_info["reason"]) if r]}
     with open(os.path.join(recordings_folder, "recording_log.yaml"), "w") as f:
         yaml.dump(log, f)
     if kpts_2d is not None:
@@ -126,7 +142,7 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
 def record_and_estimate_pose_parser(extensions=False):
     """Flags of record_and_estimate_pose.py:63-78; extensions=True (what the command line uses)
     adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence,
-    --refine, --cov_floor."""
+    --refine, --cov_floor, --sync_from_pose, --max_lag."""
     p = argparse.ArgumentParser()
     p.add_argument("--camera_names", nargs="+", required=True, help="List of camera names")
     p.add_argument("--estimator_model")
@@ -148,6 +164,8 @@ def record_and_estimate_pose_parser(extensions=False):
         p.add_argument("--min_confidence", type=float)
         p.add_argument("--refine", choices=["unit", "conf", "heatmap"])   # maximum-likelihood refinement
         p.add_argument("--cov_floor", type=float)
+        p.add_argument("--sync_from_pose", action="store_true")   # frame offsets from the 2D keypoints
+        p.add_argument("--max_lag", type=int)
     return p
 
 

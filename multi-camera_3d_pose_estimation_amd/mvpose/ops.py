@@ -303,3 +303,42 @@ def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid:
          float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(resid), opt(observed), opt(status),
          _stream(dev))
     return out, resid, observed.to(torch.bool) if observed is not None else None, status
+
+
+def epipolar_lag_cost_plan(T: int, J: int, nv: int, max_lag: int):
+    """What epipolar_lag_cost will use for (T, J, nv, max_lag) (mvp_epipolar_lag_cost_plan): the
+    kernel's time tile in frames and the workspace bytes."""
+    tile, nbytes = ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_epipolar_lag_cost_plan", int(T), int(J), int(nv), int(max_lag), ctypes.byref(tile),
+         ctypes.byref(nbytes))
+    return tile.value, nbytes.value
+
+
+def epipolar_lag_cost(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], max_lag: int,
+                      min_conf: float = 0.0, trunc_px: float = 20.0):
+    """The epipolar lag-cost scan of pose-based frame synchronisation (mvp_epipolar_lag_cost; the
+    problem is stated in include/mvpose.h; no reference counterpart).
+
+    kpts (T, J, 3, V) float32 on the GPU, cams (n_cams, 40) float64 on the GPU; view i reads column
+    cam_idx[i] with camera cam_idx[i]'s parameters, as triangulate_robust does.  For every pair
+    (a, b), a < b, of listed views and every lag l in [-max_lag, max_lag]: the sum over frames t
+    and joints of min(d², trunc_px²), d the Sampson distance in undistorted pixels between view
+    a's keypoint at frame t and view b's at frame t + l, over the terms whose two keypoints are
+    usable (finite, conf >= min_conf).  Returns (sum (NP, 2·max_lag+1) float64, cnt likewise
+    int64, pairs: the NP (a, b) tuples in row order).  The workspace is a torch.empty on the
+    call's stream, sized by epipolar_lag_cost_plan."""
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
+    if len(lead) != 2:
+        raise ValueError(f"kpts must be (T, J, 3, V), got {tuple(kpts.shape)}")
+    T, J = int(lead[0]), int(lead[1])
+    nv = len(ci)
+    pairs = [(a, b) for a in range(nv) for b in range(a + 1, nv)]
+    _, nbytes = epipolar_lag_cost_plan(T, J, nv, max_lag)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nl = 2 * int(max_lag) + 1
+    out_sum = torch.empty((len(pairs), nl), dtype=torch.float64, device=dev)
+    out_cnt = torch.empty((len(pairs), nl), dtype=torch.int64, device=dev)
+    call("mvp_epipolar_lag_cost", _ptr(kpts), T, J, V, _ptr(cams), cams.shape[0], ci, nv, int(max_lag),
+         float(min_conf), float(trunc_px), _ptr(work), int(nbytes), _ptr(out_sum), _ptr(out_cnt), _stream(dev))
+    return out_sum, out_cnt, pairs

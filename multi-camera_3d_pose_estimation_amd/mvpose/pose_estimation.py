@@ -27,12 +27,14 @@ import torch
 import yaml
 
 from . import geometry, ops
+from . import sync as frame_sync
 from .estimator import BatchPoseEstimator
 from .hrnet import N_JOINTS
 
 
 TRIANGULATION_METHODS = ("reference", "all_views", "robust")
 REFINE_MODES = (None, "unit", "conf", "heatmap")
+SYNC_MODES = (None, "pose")
 
 
 def _check_refine(refine):
@@ -350,7 +352,7 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
 def estimate_pose_from_video(camera_names, recording_paths, model, detector_model="coco_base", model_yaml="",
                              start_end_frames=(0, -1), confidence=0, extrinsic_params_dir="",
                              recompute_kpts_2d=True, triangulation="reference", inlier_px=10.0, min_conf=0.0,
-                             return_info=False, refine=None, cov_floor=1.0):
+                             return_info=False, refine=None, cov_floor=1.0, sync=None, max_lag=60):
     """pose_estimation.py:259-327.  recompute_kpts_2d replaces the reference's interactive
     y/n prompt when kpts_2d.npy already exists (:287-289).
 
@@ -359,10 +361,20 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
     min_conf) list every camera in camera_names.  return_info appends get_pose_3D's info
     dict to the returned tuple.  refine / cov_floor: get_pose_3D's maximum-likelihood refinement
     of the triangulated points ("heatmap" reads this run's heatmaps_2d, so it needs the 2D stage
-    to run: recompute_kpts_2d, or no kpts_2d.npy yet)."""
+    to run: recompute_kpts_2d, or no kpts_2d.npy yet).
+
+    sync: None (default: frame t of every camera is taken to show the same instant) or "pose":
+    after the 2D stage the cameras' frame offsets are estimated from the keypoints
+    (sync.estimate_frame_offsets over all cameras in camera_names, lags of -max_lag..max_lag
+    frames), kpts_2d and heatmaps_2d are cut to the common instants (sync.apply_frame_offsets) and
+    the aligned arrays are triangulated and returned.  ValueError, naming the cameras, when an
+    offset cannot be fixed.  info then also holds "frame_offsets" (V,) int64, "frame_first" (each
+    camera's first kept frame) and "sync_pairs", estimate_frame_offsets' pair table."""
     if triangulation not in TRIANGULATION_METHODS:
         raise ValueError(f"triangulation {triangulation!r}: one of {TRIANGULATION_METHODS}")
     _check_refine(refine)
+    if sync not in SYNC_MODES:
+        raise ValueError(f"sync {sync!r}: one of {SYNC_MODES}")
     index_name, _origin = geometry.load_camera_names(extrinsic_params_dir)
     name_index = {v: k for k, v in index_name.items()}
     camera_indices = [name_index[n] for n in camera_names]
@@ -384,6 +396,16 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
                                     frame_hw=tuple(frames[camera_indices[0]].shape[1:3]))
         kpts_2d, heatmaps = run_pose_est(model, confidence=confidence, camera_indices=camera_indices,
                                          recording_paths=frames, start_end_frames=(0, None))
+    sync_info = {}
+    if sync == "pose":
+        offsets, pair_info = frame_sync.estimate_frame_offsets(kpts_2d, camera_params, max_lag=max_lag)
+        lost = [camera_names[v] for v in np.flatnonzero(offsets == frame_sync.NO_OFFSET)]
+        if lost:
+            why = [f"{camera_names[a]}-{camera_names[b]}: {r}"
+                   for (a, b), r in zip(pair_info["pairs"], pair_info["reason"]) if r]
+            raise ValueError(f"sync='pose': no frame offset for camera(s) {lost} (rejected pairs: {why})")
+        (kpts_2d, heatmaps), first = frame_sync.apply_frame_offsets([kpts_2d, heatmaps], offsets, (3, 1))
+        sync_info = {"frame_offsets": offsets, "frame_first": first, "sync_pairs": pair_info}
     if triangulation == "reference" and refine is None:
         listed = [0, 1]
         kpts_3d = get_pose_3D(camera_params, kpts_2d, camera_indices=listed)
@@ -393,6 +415,7 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
         kpts_3d, info = get_pose_3D(camera_params, kpts_2d, camera_indices=listed, method=triangulation,
                                     inlier_px=inlier_px, min_conf=min_conf, return_info=True, refine=refine,
                                     heatmaps_2d=heatmaps, cov_floor=cov_floor)
+    info.update(sync_info)
     if return_info:
         return kpts_2d, heatmaps, kpts_3d, info
     return kpts_2d, heatmaps, kpts_3d
