@@ -641,6 +641,61 @@ int mvp_epipolar_lag_cost(const float* kpts_dev, int T, int J, int V, const doub
                           void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Cross-view association of 2D skeletons: which skeleton of camera a and which of camera b are
+ * the same person (no reference counterpart; the reference handles one person per camera).  Per
+ * frame, the skeletons of all listed views are scored against each other by the epipolar
+ * constraint of the block above and grouped so that a group holds at most one skeleton per view.
+ *
+ * kpts_dev [T][P][J][3][V] float32: kpts[:, p] is the kpts_2d layout of person slot p.  Slots are
+ * independent per view (slot p of view a and slot p of view b need not be the same person); a slot
+ * is empty when its keypoints are NaN.  cams_dev, cam_idx_host / n_cam_idx = nv as for
+ * mvp_triangulate_robust: view i reads column cam_idx[i] and the parameters of camera cam_idx[i].
+ *   Nodes: node n = i·P + p stands for (view position i, slot p); N = nv·P <= 64.
+ *   Usable keypoint, ideal pixel x = (u, v, 1), F_ab, squared Sampson distance d²: exactly those of
+ *     the epipolar lag-cost scan (min_conf as there).  A node is usable when at least min_joints of
+ *     its J keypoints are usable.
+ *   Affinity, fp64: for nodes n of view a and m of view b, a < b, over the joints usable in both
+ *     nodes, skipping the terms whose denominator is 0 or whose d² is not finite:
+ *       c(n, m) = mean_j min(d_j², trunc_px²)
+ *     defined when at least min_joints terms remain, else "undefined", stored as −1.  Each
+ *     unordered node pair is computed once: the matrix is symmetric by construction.
+ *   Grouping, per frame: clusters start as the usable nodes, one each.  link(A, B) is the maximum
+ *     of the defined affinities between a node of A and a node of B (complete linkage), undefined
+ *     when there is none; the pair (A, B) is admissible when A and B share no view.  Repeat: among
+ *     the admissible pairs with a defined link <= max_cost_px², merge the one with the smallest
+ *     link, ties broken by the smallest (smallest node of A, smallest node of B) with A the
+ *     cluster whose smallest node is smaller; stop when there is no such pair.  With undefined
+ *     stored as −1, the links of a merged cluster are the element-wise maximum of two rows.
+ *     0 < max_cost_px < trunc_px, so a link of exactly trunc_px² is never merged.
+ *   Numbering: the final clusters, sorted by the key (−number of views in the cluster, smallest
+ *     node), are groups 0, 1, ...
+ * Arithmetic is fp64 with FMA contraction allowed; no atomics, so the same inputs give the same
+ * bits on every call.  The group numbers equal those of an exact evaluation of the above whenever
+ * every comparison the algorithm makes (a link against max_cost_px², the best link of a round
+ * against the second best) has a relative margin above 1e-9.  max_cost_px and trunc_px are the
+ * float32 values given, squared in fp64.
+ *
+ * mvp_associate_views_plan : checks (T, P, J, n_cam_idx) and the four parameters as the call
+ *   does, and reports the LDS bytes of the association kernel's workgroup (one wavefront per
+ *   frame, csrc/associate.hip) and the workspace size in bytes (either may be NULL).
+ * mvp_associate_views : workspace_dev >= the plan's bytes, owned by the caller (it holds the
+ *   undistorted pixels and the F matrices; its contents are scratch).
+ *   out_group_dev [T][nv][P] int8: the node's group number, −1 for a node that is not usable.
+ *   out_count_dev [T][2] uint8: {groups, groups seen by at least 2 views}.
+ *   out_affinity_dev [T][NP][P][P] float64 or NULL: c of (view a slot p, view b slot q) for pair
+ *     (a, b) in the pair order of the lag-cost scan, −1 where undefined.
+ *   Requires T >= 1, 2 <= nv <= 8, P >= 1, nv·P <= 64, 1 <= J <= 255, T·P·J < 2^31,
+ *   0 < max_cost_px < trunc_px both finite, 1 <= min_joints <= J, min_conf not NaN.
+ *   Stream-ordered: no host synchronisation and no allocation inside the call.
+ * ------------------------------------------------------------------------- */
+int mvp_associate_views_plan(int T, int P, int J, int n_cam_idx, float min_conf, float trunc_px, float max_cost_px,
+                             int min_joints, int* lds_bytes, int64_t* workspace_bytes);
+int mvp_associate_views(const float* kpts_dev, int T, int P, int J, int V, const double* cams_dev, int n_cams,
+                        const int* cam_idx_host, int n_cam_idx, float min_conf, float trunc_px, float max_cost_px,
+                        int min_joints, void* workspace_dev, int64_t workspace_bytes, int8_t* out_group_dev,
+                        uint8_t* out_count_dev, double* out_affinity_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's
  * recordings (utils.py:849-909 read_video_as_frames; synchronize_videos.py:64,240 writes them with
  * cv2.VideoWriter_fourcc(*'mp4v')).  Simple Profile: I / P-VOPs, video packets, H.263 or MPEG

@@ -27,14 +27,15 @@
 //                written to [pair][tile][lag].
 //   reduce       one workgroup per (lag, pair): each lane adds the tiles tid, tid + 256, ... in
 //                that order, then a fixed binary tree in LDS.
-// No atomics anywhere: the same inputs give the same bits on every call.
+// No atomics anywhere: the same inputs give the same bits on every call.  The first two launches
+// are in sync_common.h: mvp_associate_views (associate.hip) starts with the same two.
 //
 // Tile: B frames of a, and as many lags per chunk as fit in 60 KiB of LDS beside them (J = 17:
 // B = 32, up to 130 lags, so L = 60 is one chunk of 121; 58 752 B + 3 KiB, two workgroups per CU).
 // Register / LDS / occupancy figures and the measurements are in DESIGN.md §4.10.
 #pragma clang fp contract(off)
 
-#include "tri_common.h"
+#include "sync_common.h"
 
 namespace {
 
@@ -42,18 +43,11 @@ constexpr int kSyBlock = 256;
 constexpr int kSyMaxTile = 64;            // frames of view a per workgroup
 constexpr int kSyLdsBytes = 60 * 1024;    // the two staged tiles; 4 KiB beside them for the block reduction
 constexpr int kSyMaxJoints = 1024;        // a frame of a's lines and one of b (6 units) must fit in the LDS budget
-constexpr int kSyMaxPairs = kMaxCams * (kMaxCams - 1) / 2;
-
-struct SyncPairs {
-    unsigned char a[kSyMaxPairs], b[kSyMaxPairs];   // positions in cam_idx
-};
 
 struct SyncPlan {
     int tile, lag_chunk, n_tiles, n_lags, n_chunks, n_pairs;
     int64_t off_und, off_f, off_psum, off_pcnt, bytes;
 };
-
-inline int64_t sy_align256(int64_t b) { return (b + 255) / 256 * 256; }
 
 // Frames are counted in units of J·8 bytes: a frame of view a costs 4 such units (its lines are
 // 32 B per keypoint), a frame of b two.  The tile takes at most 6/14 of the budget, the rest holds
@@ -89,77 +83,6 @@ inline SyncPlan sync_plan(const char* fn, int T, int J, int nv, int L) {
     b = sy_align256(b + (int64_t)pl.n_pairs * pl.n_tiles * pl.n_lags * 4);
     pl.bytes = b;
     return pl;
-}
-
-// inverse of a 3x3 matrix by its adjugate (row-major)
-__device__ __forceinline__ void inv3(const double* m, double (&o)[9]) {
-    const double c0 = m[4] * m[8] - m[5] * m[7];
-    const double c1 = m[5] * m[6] - m[3] * m[8];
-    const double c2 = m[3] * m[7] - m[4] * m[6];
-    const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
-    const double id = 1.0 / det;
-    o[0] = c0 * id;
-    o[1] = (m[2] * m[7] - m[1] * m[8]) * id;
-    o[2] = (m[1] * m[5] - m[2] * m[4]) * id;
-    o[3] = c1 * id;
-    o[4] = (m[0] * m[8] - m[2] * m[6]) * id;
-    o[5] = (m[2] * m[3] - m[0] * m[5]) * id;
-    o[6] = c2 * id;
-    o[7] = (m[1] * m[6] - m[0] * m[7]) * id;
-    o[8] = (m[0] * m[4] - m[1] * m[3]) * id;
-}
-
-// F_ab = K_b⁻ᵀ [t]ₓ R K_a⁻¹, R = R_b R_aᵀ, t = T_b − R T_a: x_bᵀ F x_a = 0 for matched pixels.
-__global__ void sync_fundamental_kernel(const double* __restrict__ cams, CamIdx ci, SyncPairs pr, int n_pairs,
-                                        double* __restrict__ fmat) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_pairs) return;
-    const double* ca = cams + (int64_t)ci.v[pr.a[p]] * MVP_CAM_DOUBLES;
-    const double* cb = cams + (int64_t)ci.v[pr.b[p]] * MVP_CAM_DOUBLES;
-    const double *Ra = ca + 14, *Ta = ca + 23, *Rb = cb + 14, *Tb = cb + 23;
-    double R[9], t[3], E[9], Kai[9], Kbi[9], M[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) R[3 * i + j] = Rb[3 * i] * Ra[3 * j] + Rb[3 * i + 1] * Ra[3 * j + 1] + Rb[3 * i + 2] * Ra[3 * j + 2];
-#pragma unroll
-    for (int i = 0; i < 3; i++) t[i] = Tb[i] - (R[3 * i] * Ta[0] + R[3 * i + 1] * Ta[1] + R[3 * i + 2] * Ta[2]);
-    // E = [t]ₓ R
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        E[j] = t[1] * R[6 + j] - t[2] * R[3 + j];
-        E[3 + j] = t[2] * R[j] - t[0] * R[6 + j];
-        E[6 + j] = t[0] * R[3 + j] - t[1] * R[j];
-    }
-    inv3(ca, Kai);
-    inv3(cb, Kbi);
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) M[3 * i + j] = E[3 * i] * Kai[j] + E[3 * i + 1] * Kai[3 + j] + E[3 * i + 2] * Kai[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) fmat[9 * p + 3 * i + j] = Kbi[i] * M[j] + Kbi[3 + i] * M[3 + j] + Kbi[6 + i] * M[6 + j];
-}
-
-// und[i][e] = the f32 undistorted pixel of view i's keypoint e = t·J + j, NaN when not usable.
-__global__ __launch_bounds__(kBlock) void sync_undistort_kernel(const float* __restrict__ kpts, int64_t n, int V,
-                                                                const double* __restrict__ cams, int n_cams,
-                                                                CamIdx ci, float min_conf, float2* __restrict__ und) {
-    __shared__ double scam[kMaxCams][MVP_CAM_DOUBLES];
-    __shared__ CamFast sfast[kMaxCams];
-    load_cams(scam, sfast, cams, n_cams);  // ends in the block's barrier
-    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (e >= n) return;
-    const int col = ci.v[blockIdx.y];
-    const float* __restrict__ kp = kpts + e * 3 * V;
-    const float x = kp[col], y = kp[V + col], c = kp[2 * V + col];
-    float ux, uy;
-    undistort_point(x, y, scam[col], ux, uy);
-    const bool ok = view_usable(x, y, c, min_conf);
-    const float qnan = __builtin_nanf("");
-    und[(int64_t)blockIdx.y * n + e] = make_float2(ok ? ux : qnan, ok ? uy : qnan);
 }
 
 // A staged keypoint of view b: its f32 pixel and (Fᵀ x_b)₀² + (Fᵀ x_b)₁².
@@ -315,13 +238,7 @@ extern "C" int mvp_epipolar_lag_cost(const float* kpts, int T, int J, int V, con
     MVP_REQUIRE(kpts && cams && workspace && out_sum && out_cnt, "%s: null device pointer", fn);
     const int64_t n = (int64_t)T * J;
     SyncPairs pr{};
-    int np = 0;
-    for (int a = 0; a < n_cam_idx; a++)
-        for (int b = a + 1; b < n_cam_idx; b++) {
-            pr.a[np] = (unsigned char)a;
-            pr.b[np] = (unsigned char)b;
-            np++;
-        }
+    const int np = sync_list_pairs(n_cam_idx, pr);
     char* ws = static_cast<char*>(workspace);
     float2* und = reinterpret_cast<float2*>(ws + pl.off_und);
     double* fmat = reinterpret_cast<double*>(ws + pl.off_f);

@@ -105,6 +105,11 @@ SIGNATURES = {
     "mvp_epipolar_lag_cost_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int), P(c_int64)]),
     "mvp_epipolar_lag_cost": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_int, c_float,
                                       c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mvp_associate_views_plan": (c_int, [c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_int, P(c_int),
+                                         P(c_int64)]),
+    "mvp_associate_views": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_float,
+                                    c_float, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -342,3 +342,49 @@ def epipolar_lag_cost(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[
     call("mvp_epipolar_lag_cost", _ptr(kpts), T, J, V, _ptr(cams), cams.shape[0], ci, nv, int(max_lag),
          float(min_conf), float(trunc_px), _ptr(work), int(nbytes), _ptr(out_sum), _ptr(out_cnt), _stream(dev))
     return out_sum, out_cnt, pairs
+
+
+def associate_views_plan(T: int, P: int, J: int, nv: int, *, min_conf: float = 0.0, trunc_px: float = 20.0,
+                         max_cost_px: float = 8.0, min_joints: int = 5):
+    """What associate_views will use for (T, P, J, nv) (mvp_associate_views_plan, which refuses
+    what the call refuses): the LDS bytes of a frame's workgroup and the workspace bytes."""
+    lds, nbytes = ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_associate_views_plan", int(T), int(P), int(J), int(nv), float(min_conf), float(trunc_px),
+         float(max_cost_px), int(min_joints), ctypes.byref(lds), ctypes.byref(nbytes))
+    return lds.value, nbytes.value
+
+
+def associate_views(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], *, min_conf: float = 0.0,
+                    trunc_px: float = 20.0, max_cost_px: float = 8.0, min_joints: int = 5,
+                    return_affinity: bool = False):
+    """Which 2D skeletons of the listed views are the same person (mvp_associate_views; the
+    problem is stated in include/mvpose.h; no reference counterpart).
+
+    kpts (T, P, J, 3, V) float32 on the GPU: kpts[:, p] is the kpts_2d layout of person slot p;
+    slots are independent per view and an empty slot is NaN.  cams (n_cams, 40) float64 on the
+    GPU; view i reads column cam_idx[i] with camera cam_idx[i]'s parameters, as triangulate_robust
+    does.  Per frame, nodes (view, slot) with at least min_joints usable keypoints (finite,
+    conf >= min_conf) are grouped by complete-linkage agglomeration on the mean truncated squared
+    Sampson distance of their common joints, merging while the link is <= max_cost_px² and never
+    two nodes of one view.  Returns (group (T, NV, P) int8: the node's group number, -1 for a node
+    that is not usable, groups ordered by (-views, smallest node); count (T, 2) uint8: groups and
+    groups seen by at least two views; affinity (T, NP, P, P) float64 with -1 for undefined, or
+    None; pairs: the NP (a, b) tuples in row order).  The workspace is a torch.empty on the call's
+    stream, sized by associate_views_plan."""
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
+    if len(lead) != 3:
+        raise ValueError(f"kpts must be (T, P, J, 3, V), got {tuple(kpts.shape)}")
+    T, P, J = (int(d) for d in lead)
+    nv = len(ci)
+    pairs = [(a, b) for a in range(nv) for b in range(a + 1, nv)]
+    _, nbytes = associate_views_plan(T, P, J, nv, min_conf=min_conf, trunc_px=trunc_px, max_cost_px=max_cost_px,
+                                     min_joints=min_joints)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    group = torch.empty((T, nv, P), dtype=torch.int8, device=dev)
+    count = torch.empty((T, 2), dtype=torch.uint8, device=dev)
+    aff = torch.empty((T, len(pairs), P, P), dtype=torch.float64, device=dev) if return_affinity else None
+    call("mvp_associate_views", _ptr(kpts), T, P, J, V, _ptr(cams), cams.shape[0], ci, nv, float(min_conf),
+         float(trunc_px), float(max_cost_px), int(min_joints), _ptr(work), int(nbytes), _ptr(group), _ptr(count),
+         _ptr(aff) if aff is not None else None, _stream(dev))
+    return group, count, aff, pairs

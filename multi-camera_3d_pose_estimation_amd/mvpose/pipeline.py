@@ -10,6 +10,10 @@ With refine= (no reference counterpart) kpts_3d holds the maximum-likelihood ref
 triangulated points and kpts_3d_seed, kpts_3d_cov (T, 17, 3, 3), tri_refine_cost and
 tri_refine_status come with it (ops.triangulate_refine).
 
+process_people(frames, bboxes (T, V, P, 4)) is the same path for several people per camera (no
+reference counterpart): the 2D stage per person box, ops.associate_views across the cameras, then
+one kpts_2d / kpts_3d per group of skeletons that show the same person.
+
 process(..., overlap_moments=True) computes heatmaps_2d on a side stream beside the
 next batch's backbone (triangulation reads only kpts_2d); call wait(out) before reading
 heatmaps_2d on the current stream.
@@ -130,6 +134,97 @@ class MultiViewPipeline:
         for i in range(0, n, mb):
             self.detector.detect(flat[i:i + mb], best_out=self._best[i:min(n, i + mb)])
         return self._best[:n]
+
+    def detect_people(self, flat: torch.Tensor, max_people: int) -> np.ndarray:
+        """(T*V, H, W, 3) camera-frames -> host (T*V, max_people, 4) float64 xyxy: each frame's
+        first max_people detections after NMS (score-descending) with score > bbox_thr, NaN rows
+        for the slots left empty."""
+        n = flat.shape[0]
+        P = int(max_people)
+        out = torch.empty((n, P, 4), dtype=torch.float32, device=self.device)
+        slot = torch.arange(P, device=self.device)
+        mb = self.detector.max_batch
+        for i in range(0, n, mb):
+            dets, counts = self.detector.nms_device(self.detector.detect(flat[i:i + mb]))
+            top = dets[:, :P]
+            if top.shape[1] < P:
+                top = torch.cat([top, top.new_zeros((top.shape[0], P - top.shape[1], 5))], 1)
+            ok = (slot[None, :] < counts[:, None]) & (top[..., 4] > self.bbox_thr)
+            out[i:i + mb] = torch.where(ok[..., None], top[..., :4], top.new_full((), float("nan")))
+        return out.cpu().numpy().astype(np.float64)
+
+    def process_people(self, frames: torch.Tensor, bboxes=None, max_people: int = 4, max_groups: int | None = None,
+                       **assoc_kw) -> dict:
+        """Several people per camera (no reference counterpart): the 2D stage on every person box,
+        ops.associate_views across camera_indices, then robust triangulation per group.
+
+        frames (T, V, H, W, 3) uint8 on the GPU.  bboxes: host (T, V, P, 4) xyxy person boxes, NaN
+        rows for empty slots; the slot order is free and independent per camera-frame.  None: the
+        detector's first max_people detections after NMS with score > bbox_thr (P = max_people).
+        The 2D stage runs on the non-empty (camera-frame, slot) rows only, in that order, in chunks
+        of the estimator's max_frames.  max_groups: the groups kept per frame (default P).
+        assoc_kw: trunc_px, max_cost_px, min_joints, min_conf of ops.associate_views (min_conf
+        defaults to the pipeline's).  Returns, device-resident:
+            kpts_2d_people     (T, P, 17, 3, V) float32   per slot, NaN for empty slots
+            heatmaps_2d_people (T, V, P, 17, 6) float64   likewise
+            people_group       (T, NV, P) int8            group of (view position, slot), -1 = none
+            people_count       (T, 2) uint8               groups, groups seen by >= 2 views
+            people_dropped     (T,) int64                 groups beyond max_groups, not returned
+            kpts_2d            (T, G, 17, 3, V) float32   per group, NaN where a view has no member
+            heatmaps_2d        (T, G, V, 17, 6) float64
+            kpts_3d            (T, G, 17, 3) float32      ops.triangulate_robust over camera_indices
+            tri_inliers        (T, G, 17, NV) bool, tri_reproj_err (T, G, 17, NV) float32
+        and with refine= also kpts_3d_seed, kpts_3d_cov (T, G, 17, 3, 3), tri_refine_cost and
+        tri_refine_status (T, G, 17), kpts_3d then holding the refined points (as process())."""
+        from . import people
+        T, V = frames.shape[:2]
+        if V != self.n_views:
+            raise ValueError(f"frames carry {V} views, pipeline has {self.n_views} cameras")
+        flat = frames.reshape(T * V, *frames.shape[2:])
+        if bboxes is None:
+            if self.detector is None:
+                raise ValueError("process_people needs person boxes: pass bboxes or build the pipeline with a detector")
+            boxes = self.detect_people(flat, max_people)
+        else:
+            boxes = np.asarray(bboxes.cpu() if isinstance(bboxes, torch.Tensor) else bboxes, dtype=np.float64)
+            if boxes.ndim != 4 or boxes.shape[:2] != (T, V) or boxes.shape[3] != 4 or boxes.shape[2] < 1:
+                raise ValueError(f"bboxes must be (T, V, P, 4) = ({T}, {V}, P, 4), got {boxes.shape}")
+        P = boxes.shape[-2]
+        boxes = boxes.reshape(T * V, P, 4)
+        row_f, row_p = np.nonzero(np.isfinite(boxes).all(-1))       # (camera-frame, slot) order
+        kp = torch.full((T * V, P, N_JOINTS, 3), float("nan"), dtype=torch.float32, device=self.device)
+        gauss = torch.full((T * V, P, N_JOINTS, 6), float("nan"), dtype=torch.float64, device=self.device)
+        step = self.estimator.max_frames
+        for i in range(0, len(row_f), step):
+            f = torch.as_tensor(row_f[i:i + step], device=self.device)
+            p = torch.as_tensor(row_p[i:i + step], device=self.device)
+            r = self.estimator.run(flat.index_select(0, f), bboxes=boxes[row_f[i:i + step], row_p[i:i + step]])
+            kp[f, p] = torch.cat([r["keypoints"], r["scores"][..., None]], -1)
+            gauss[f, p] = r["gaussians"]
+        out = {"kpts_2d_people": kp.reshape(T, V, P, N_JOINTS, 3).permute(0, 2, 3, 4, 1).contiguous(),
+               "heatmaps_2d_people": gauss.reshape(T, V, P, N_JOINTS, 6)}
+        assoc_kw.setdefault("min_conf", self.min_conf)
+        out["people_group"], out["people_count"], _, _ = ops.associate_views(
+            out["kpts_2d_people"], self.cams, self.camera_indices, **assoc_kw)
+        G = P if max_groups is None else int(max_groups)
+        out["kpts_2d"], out["heatmaps_2d"], out["people_dropped"] = people.gather_groups(
+            out["kpts_2d_people"], out["people_group"], self.camera_indices, G, gauss=out["heatmaps_2d_people"])
+        out["kpts_3d"], out["tri_inliers"], out["tri_reproj_err"] = ops.triangulate_robust(
+            out["kpts_2d"], self.cams, self.camera_indices, inlier_px=self.inlier_px, min_conf=self.min_conf)
+        if self.refine is not None:
+            # triangulate_refine takes the heatmap Gaussians per (frame, view, joint): groups fold into frames
+            nv = len(self.camera_indices)
+            out["kpts_3d_seed"] = out["kpts_3d"]
+            xyz, cov, cost, status = ops.triangulate_refine(
+                out["kpts_2d"].reshape(T * G, N_JOINTS, 3, V), self.cams, self.camera_indices,
+                out["kpts_3d_seed"].reshape(T * G, N_JOINTS, 3), weights=self.refine,
+                gauss=out["heatmaps_2d"].reshape(T * G, V, N_JOINTS, 6) if self.refine == "heatmap" else None,
+                mask=out["tri_inliers"].reshape(T * G, N_JOINTS, nv), min_conf=self.min_conf, cov_floor=self.cov_floor)
+            out["kpts_3d"] = xyz.reshape(T, G, N_JOINTS, 3)
+            out["kpts_3d_cov"] = cov.reshape(T, G, N_JOINTS, 3, 3)
+            out["tri_refine_cost"] = cost.reshape(T, G, N_JOINTS)
+            out["tri_refine_status"] = status.reshape(T, G, N_JOINTS)
+        return out
 
     @staticmethod
     def wait(out: dict) -> None:

@@ -588,9 +588,11 @@ class RTMDetector:
         out[ok] = b[ok, :4]
         return out
 
-    def nms(self, det: dict):
-        """mmdet's post-processing on detect()'s candidates -> list of (M, 6) numpy
-        [x1, y1, x2, y2, score, label] per frame (score-descending, label 0 = person)."""
+    def nms_device(self, det: dict):
+        """mmdet's post-processing on detect()'s candidates, left on the device: dets (n, cap, 5)
+        f32 [x1, y1, x2, y2, score] per frame, score-descending, and counts (n,) int32, the rows
+        of each frame that are detections (cap = max_per_img; the rows past a frame's count carry
+        no meaning).  Stream-ordered, no host synchronisation."""
         cand = det["cand"]
         n = cand.shape[0]
         cap = self.cfg["max_per_img"]
@@ -602,6 +604,13 @@ class RTMDetector:
              int(self.cfg["nms_pre"]), ctypes.c_float(self.cfg["score_thr"]), ctypes.c_float(self.cfg["iou_threshold"]),
              cap, ctypes.c_float(fx), ctypes.c_float(fy), ctypes.c_void_p(dets.data_ptr()),
              ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(cand.device).cuda_stream))
+        return dets, counts
+
+    def nms(self, det: dict):
+        """mmdet's post-processing on detect()'s candidates -> list of (M, 6) numpy
+        [x1, y1, x2, y2, score, label] per frame (score-descending, label 0 = person)."""
+        dets, counts = self.nms_device(det)
+        n = dets.shape[0]
         d, c = dets.cpu().numpy(), counts.cpu().numpy()
         out = []
         for i in range(n):
