@@ -285,8 +285,6 @@ __global__ __launch_bounds__(512, 2) void basic_block_c32_kernel(BlockParams p) 
     }
 }
 
-int g_cus = 0;
-
 }  // namespace
 
 bool basic_block_c32_supported(int H, int W) { return W == 48 && H % 8 == 0; }
@@ -304,13 +302,8 @@ void launch_basic_block_c32(const uint16_t* x, const uint16_t* w1, const float* 
                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
         attr = true;
     }
-    if (g_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     BlockParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, H, (int)((long)N * (H / C::TH))};
-    const int grid = std::min(p.n_tiles, g_cus);
+    const int grid = std::min(p.n_tiles, cu_count());
     hipLaunchKernelGGL(basic_block_c32_kernel<48>, dim3(grid), dim3(C::NT), C::LDS, s, p);
     MVP_HIP(hipGetLastError());
 }

@@ -589,8 +589,6 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BNParams p) {
         c2_role<LEAD>(p, lds, wave - 4, lane, crop0, n_steps);
 }
 
-int g_bn_cus = 0;
-
 }  // namespace
 
 bool bneck_supported(int H, int W, int C, int M) {
@@ -608,7 +606,7 @@ void launch_bneck_t(const BNParams& p, hipStream_t s) {
                                     BNT<LEAD>::LDS));
         attr = true;
     }
-    const int grid = std::min(p.N, g_bn_cus);
+    const int grid = std::min(p.N, cu_count());
     hipLaunchKernelGGL(bneck_kernel<LEAD>, dim3(grid), dim3(512), BNT<LEAD>::LDS, s, p);
     MVP_HIP(hipGetLastError());
 }
@@ -617,11 +615,6 @@ void launch_bneck(const BneckLaunch& c, hipStream_t s) {
     MVP_REQUIRE(c.H == BNT<false>::H && c.W == BNT<false>::W, "bneck: plane %dx%d", c.H, c.W);
     MVP_REQUIRE(c.N >= 0 && c.N < (1 << 24), "bneck: %d crops", c.N);
     if (c.N == 0) return;
-    if (g_bn_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_bn_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     MVP_REQUIRE(!(c.lead && c.planar), "bneck: planar output is for the 256-ch blocks");
     BNParams p{c.x, c.w1, c.b1, c.w2, c.b2, c.w3, c.b3, c.y, c.N, c.perm ? 1 : 0, c.planar ? 1 : 0};
     if (c.lead)

@@ -400,17 +400,7 @@ __global__ __launch_bounds__(NW * 64, 2) void conv_mfma_kernel(ConvParams p) {
     }
 }
 
-int g_num_cus = 0;
 uint16_t* g_zero = nullptr;
-
-int num_cus() {
-    if (g_num_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_num_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    return g_num_cus;
-}
 
 uint16_t* g_sink = nullptr;
 
@@ -446,7 +436,7 @@ int blocks_per_cu(int lds) {
 template <int KS, int S, int BM, int TH, int TW, int NB, int NBUF, int NW>
 void launch_ring(const ConvParams& p, int lds, int per_cu, hipStream_t s) {
     const int y_blocks = p.Cout_pad / BM;
-    long gx = ((long)num_cus() * per_cu + y_blocks - 1) / y_blocks;
+    long gx = ((long)cu_count() * per_cu + y_blocks - 1) / y_blocks;
     if (gx > p.n_tiles) gx = p.n_tiles;
     hipLaunchKernelGGL((conv_mfma_kernel<KS, S, BM, TH, TW, NB, NBUF, NW>), dim3((unsigned)gx, (unsigned)y_blocks),
                        dim3(NW * 64), lds, s, p);
@@ -843,14 +833,8 @@ void launch_stem(const uint16_t* x, const float* w, const float* bias, uint16_t*
     const long total = (long)N * Ho * Wo * 4;
     if (total == 0) return;
     if (Wo == 96 && H % 2 == 0 && Ho % 2 == 0) {  // the 256x192 crop: MFMA path
-        static int cus = 0;
-        if (cus == 0) {
-            int dev = 0;
-            MVP_HIP(hipGetDevice(&dev));
-            MVP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        }
         const long n_tiles = (long)N * Ho / 2;
-        const long grid = std::min<long>(n_tiles, (long)cus * 8);
+        const long grid = std::min<long>(n_tiles, (long)cu_count() * 8);
         hipLaunchKernelGGL(stem_mfma_kernel<96>, dim3((unsigned)grid), dim3(256), 0, s, x, w, bias, y, H, Ho,
                            n_tiles);
         MVP_HIP(hipGetLastError());

@@ -505,8 +505,6 @@ __global__ __launch_bounds__(256) void head_fuse_kernel(HeadFuse p) {
     }
 }
 
-int g_cus1 = 0;
-
 template <int BM, int KCH>
 void launch_1x1(const P1x1& p, int cout_pad, hipStream_t s) {
     constexpr int lds = KCH * 4 * BM * 16;
@@ -517,14 +515,9 @@ void launch_1x1(const P1x1& p, int cout_pad, hipStream_t s) {
         MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds));
         if (per_cu < 1) per_cu = 1;
     }
-    if (g_cus1 == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_cus1, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const int y_blocks = cout_pad / BM;
     const long units = (p.n_pix + 16 * kPTW - 1) / (16 * kPTW);
-    long gx = ((long)g_cus1 * per_cu + y_blocks - 1) / y_blocks;
+    long gx = ((long)cu_count() * per_cu + y_blocks - 1) / y_blocks;
     gx = std::min(gx, (units + 3) / 4);
     hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)y_blocks), dim3(256), lds, s, p);
     MVP_HIP(hipGetLastError());
@@ -557,11 +550,6 @@ void launch_conv1x1_pair(const PairLaunch& c, hipStream_t s) {
     if (c.n_pix == 0) return;
     PPair p{c.x, c.x2, c.c1, c.x2 ? c.c2 : 0, c.c1 / 32, c.w1, c.b1, c.res, c.y, c.w2, c.b2, c.y2,
             conv_zero_region(), c.n_pix};
-    if (g_cus1 == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_cus1, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const long units = (c.n_pix + 15) / 16;
     auto go = [&](auto kern, int kch) {
         const int kPairThreads = kch == 2 ? pair_threads<2>() : pair_threads<4>();
@@ -570,7 +558,7 @@ void launch_conv1x1_pair(const PairLaunch& c, hipStream_t s) {
         int pc = 0;
         MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, kPairThreads, lds));
         if (pc < 1) pc = 1;
-        const long grid = std::min<long>((long)g_cus1 * pc, (units + kPairThreads / 64 - 1) / (kPairThreads / 64));
+        const long grid = std::min<long>((long)cu_count() * pc, (units + kPairThreads / 64 - 1) / (kPairThreads / 64));
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPairThreads), lds, s, p);
     };
     // look-ahead depth (units in flight per wave) as measured best per join: 64-ch 1 (1,496 vs
@@ -600,11 +588,6 @@ bool launch_conv1x1_wide(const ConvLaunch& c, hipStream_t s) {
     if (n_pix == 0) return true;
     PPair p{c.x, c.x2, 64, cin == 128 ? 64 : 0, 2, c.w, c.bias, c.res, c.y, nullptr, nullptr,
             nullptr, conv_zero_region(), n_pix};
-    if (g_cus1 == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_cus1, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const long units = (n_pix + 15) / 16;
     auto go = [&](auto kern, int kch) {
         const int lds = kch * 4 * 256 * 16 + 8 * 4096;
@@ -612,7 +595,7 @@ bool launch_conv1x1_wide(const ConvLaunch& c, hipStream_t s) {
         int pc = 0;
         MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, 512, lds));
         if (pc < 1) pc = 1;
-        const long grid = std::min<long>((long)g_cus1 * pc, (units + 7) / 8);
+        const long grid = std::min<long>((long)cu_count() * pc, (units + 7) / 8);
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, p);
     };
     if (cin == 64) go(conv1x1_pair_kernel<2, true, 1, false>, 2);

@@ -1,5 +1,5 @@
-// Internal (not part of the C-ABI): person-detector kernels (det.hip) used by the
-// detector graph runtime (detnet.cpp).
+// Internal (not part of the C-ABI): person-detector kernels (det_*.hip, one kernel family per
+// file; det.hip routes a conv to its family) used by the detector graph runtime (detnet.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

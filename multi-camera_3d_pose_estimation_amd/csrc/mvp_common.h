@@ -36,6 +36,22 @@ inline void hip_check(hipError_t e, const char* what, const char* file, int line
         if (!(cond)) ::mvp::fail(MVP_ERR_ARG, __VA_ARGS__);      \
     } while (0)
 
+namespace mvp {
+
+// CUs of the device, queried on first use and cached for the process (not per device: the
+// first device's count serves all); hidden: not one of the library's dynamic symbols
+__attribute__((visibility("hidden"))) inline int cu_count() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        MVP_HIP(hipGetDevice(&dev));
+        MVP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        return n;
+    }();
+    return cus;
+}
+
+}  // namespace mvp
+
 // Wrap an exported function body: converts exceptions into codes + last error.
 #define MVP_ABI_BEGIN try {
 #define MVP_ABI_END                                              \

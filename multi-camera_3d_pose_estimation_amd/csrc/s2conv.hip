@@ -295,7 +295,6 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int g_s_cus = 0;
 uint16_t* g_s_sink = nullptr;
 
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM, bool PM>
@@ -307,7 +306,7 @@ void launch_sp_pm(SParams p, hipStream_t s) {
         MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    const int grid = std::min(p.n_tiles, g_s_cus);
+    const int grid = std::min(p.n_tiles, cu_count());
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT_THREADS), G::LDS, s, p);
 }
 
@@ -320,12 +319,7 @@ void launch_sp(SParams p, hipStream_t s) {
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM>
 void launch_s(const ConvLaunch& c, hipStream_t s) {
     using G = SCfg<CIN, H, W, TH, NB, WRES, BM>;
-    if (g_s_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_s_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
-    }
+    if (!g_s_sink) MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
     MVP_REQUIRE(!WRES || c.Cout == BM, "s2conv: resident weights need Cout == BM");
     MVP_REQUIRE(c.Cout % BM == 0, "s2conv: Cout %d not a multiple of %d", c.Cout, BM);
     MVP_REQUIRE(c.Cin == CIN && c.H == H && c.W == W, "s2conv: plane mismatch");
@@ -339,12 +333,7 @@ void launch_s(const ConvLaunch& c, hipStream_t s) {
 }
 
 void init_s() {
-    if (g_s_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_s_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
-    }
+    if (!g_s_sink) MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
 }
 
 }  // namespace

@@ -578,8 +578,6 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
     }
 }
 
-int g_s2_cus = 0;
-
 }  // namespace
 
 bool stem2_supported(int H, int W, int cin2, int cout2) {
@@ -597,13 +595,8 @@ void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uin
         MVP_HIP(hipFuncSetAttribute((const void*)stem2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2S::LDS));
         attr = true;
     }
-    if (g_s2_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_s2_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const char* e = getenv("MVPOSE_STEM2_TILE");  // tests: the tile kernel (bit-identical reference)
-    if ((e && e[0] == '1') || !crop_ranges_balanced(N, g_s2_cus)) {  // + small / ragged batches
+    if ((e && e[0] == '1') || !crop_ranges_balanced(N, cu_count())) {  // + small / ragged batches
         static bool attr_t = false;
         if (!attr_t) {
             MVP_HIP(hipFuncSetAttribute((const void*)stem2_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -613,14 +606,14 @@ void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uin
         const long tiles = (long)N * (S2::H2 / S2::TR);
         MVP_REQUIRE(tiles < (1L << 30), "stem2: too many tiles");
         StemParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, (int)tiles};
-        const int grid = (int)std::min<long>(tiles, g_s2_cus);
+        const int grid = (int)std::min<long>(tiles, cu_count());
         hipLaunchKernelGGL(stem2_tile_kernel, dim3(grid), dim3(S2::NTH), S2::LDS, s, p);
         MVP_HIP(hipGetLastError());
         return;
     }
     MVP_REQUIRE(N < (1 << 24), "stem2: too many crops");
     StemParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, 0};
-    const int grid = std::min(N, g_s2_cus);
+    const int grid = std::min(N, cu_count());
     hipLaunchKernelGGL(stem2_kernel, dim3(grid), dim3(512), S2S::LDS, s, p);
     MVP_HIP(hipGetLastError());
 }

@@ -320,8 +320,6 @@ __global__ __launch_bounds__(512, 1) void tblock32_kernel(TBParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int g_tb_cus = 0;
-
 }  // namespace
 
 bool launch_tblock32(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
@@ -342,15 +340,10 @@ bool launch_tblock32(const uint16_t* x, const uint16_t* w1, const float* b1, con
         MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    if (g_tb_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_tb_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const long tiles = (long)N * (H / G::TH);
     MVP_REQUIRE(tiles < (1L << 30), "tblock: too many tiles");
     TBParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, H, (int)tiles};
-    const int grid = (int)std::min<long>(tiles, g_tb_cus);
+    const int grid = (int)std::min<long>(tiles, cu_count());
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NTH), G::LDS, s, p);
     MVP_HIP(hipGetLastError());
     return true;

@@ -463,8 +463,6 @@ __global__ __launch_bounds__(512, 1) void tblock32s_kernel(S32Params p) {
         conv2_role(p, lds, wave - 4, lane, n_strips, crop0, p.zero + ((wave * 64 + lane) & (kZeroSlots - 1)) * 8);
 }
 
-int g_s32_cus = 0;
-
 }  // namespace
 
 bool launch_tblock32s(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
@@ -480,15 +478,10 @@ bool launch_tblock32s(const uint16_t* x, const uint16_t* w1, const float* b1, co
         MVP_HIP(hipFuncSetAttribute((const void*)tblock32s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    if (g_s32_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_s32_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
-    if (!crop_ranges_balanced(N, g_s32_cus)) return false;  // small / ragged batch: the tile kernel
+    if (!crop_ranges_balanced(N, cu_count())) return false;  // small / ragged batch: the tile kernel
     MVP_REQUIRE(N < (1 << 24), "tblock32s: too many crops");
     S32Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N};
-    const int grid = std::min(N, g_s32_cus);
+    const int grid = std::min(N, cu_count());
     hipLaunchKernelGGL(tblock32s_kernel, dim3(grid), dim3(512), G::LDS, s, p);
     MVP_HIP(hipGetLastError());
     return true;

@@ -597,8 +597,6 @@ __global__ __launch_bounds__(256, 1) void tblock64_kernel(TB64Params p) {
         conv2_role<ST>(p, lds, wave - 2, lane, n_items, p.zero + ((wave * 64 + lane) & (kZeroSlots - 1)) * 8, crop0);
 }
 
-int g_tb64_cus = 0;
-
 }  // namespace
 
 bool tblock64_supported(int H, int W) {
@@ -617,20 +615,15 @@ void launch_tblock64(const uint16_t* x, const uint16_t* w1, const float* b1, con
         MVP_HIP(hipFuncSetAttribute((const void*)tblock64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    if (g_tb64_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_tb64_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const long tiles = (long)N * G::TILES_H;
     MVP_REQUIRE(tiles < (1L << 30), "tblock64: too many tiles");
     // contiguous crop ranges (conv1 reuses rows across a crop's tiles) from one crop per CU;
     // smaller batches: tiles strided over every CU, every tile computing all 10 rows
     TB64Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N, (int)tiles};
-    if (crop_ranges_balanced(N, g_tb64_cus))
-        hipLaunchKernelGGL(tblock64_kernel<false>, dim3(std::min(N, g_tb64_cus)), dim3(256), G::LDS, s, p);
+    if (crop_ranges_balanced(N, cu_count()))
+        hipLaunchKernelGGL(tblock64_kernel<false>, dim3(std::min(N, cu_count())), dim3(256), G::LDS, s, p);
     else
-        hipLaunchKernelGGL(tblock64_kernel<true>, dim3((int)std::min<long>(tiles, g_tb64_cus)), dim3(256), G::LDS, s, p);
+        hipLaunchKernelGGL(tblock64_kernel<true>, dim3((int)std::min<long>(tiles, cu_count())), dim3(256), G::LDS, s, p);
     MVP_HIP(hipGetLastError());
 }
 

@@ -313,7 +313,6 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int g_t_cus = 0;
 uint16_t* g_t_sink = nullptr;
 
 template <int CIN, int H, int W, int TH, int NB, bool WRES, bool RES, int BM, bool PM>
@@ -326,19 +325,14 @@ void launch_t_kernel(const TParams& p, hipStream_t s) {
         MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    const int grid = std::min(p.n_tiles, g_t_cus);
+    const int grid = std::min(p.n_tiles, cu_count());
     MVP_REQUIRE(grid % p.ncb == 0, "tconv: grid %d not a multiple of the %d column blocks", grid, p.ncb);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT_THREADS), G::LDS, s, p);
 }
 
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM = 64>
 void launch_t(const ConvLaunch& c, hipStream_t s) {
-    if (g_t_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_t_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        MVP_HIP(hipMalloc(&g_t_sink, 64 * 32));
-    }
+    if (!g_t_sink) MVP_HIP(hipMalloc(&g_t_sink, 64 * 32));
     MVP_REQUIRE(!WRES || c.Cout == BM, "tconv: resident weights need Cout == BM");
     MVP_REQUIRE(c.Cout % BM == 0, "tconv: Cout %d not a multiple of %d", c.Cout, BM);
     const long tiles = (long)((c.N + NB - 1) / NB) * (H / TH) * (c.Cout / BM);

@@ -313,7 +313,6 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int g_t16_cus = 0;
 uint16_t* g_t16_sink = nullptr;
 
 template <int CIN, int H, int W, int TH, int NB, int BM, bool RES>
@@ -331,21 +330,16 @@ void launch_k16(const T16Params& p, int grid, hipStream_t s) {
 template <int CIN, int H, int W, int TH, int NB, int BM>
 void launch_t16(const ConvLaunch& c, hipStream_t s) {
     static_assert(HMap<H, W, TH, NB>().balanced(), "halo residues must be balanced for the lane map");
-    if (g_t16_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_t16_cus, hipDeviceAttributeMultiprocessorCount, dev));
-        MVP_HIP(hipMalloc(&g_t16_sink, 64 * 32));
-    }
+    if (!g_t16_sink) MVP_HIP(hipMalloc(&g_t16_sink, 64 * 32));
     MVP_REQUIRE(c.Cout % BM == 0, "tconv16: Cout %d not a multiple of %d", c.Cout, BM);
     const int ncb = c.Cout / BM;
     const long n_sp = (long)((c.N + NB - 1) / NB) * (H / TH);
     const long n_sp8 = (n_sp + 7) / 8 * 8;  // XCD-major tile order: spatial tiles in groups of 8
     const long tiles = n_sp8 * ncb;
     MVP_REQUIRE(tiles < (1L << 30), "tconv16: too many tiles");
-    int grid = (int)std::min<long>(tiles, g_t16_cus);
+    int grid = (int)std::min<long>(tiles, cu_count());
     if (grid < tiles) grid -= grid % (8 * ncb);  // fixed cout block per workgroup
-    MVP_REQUIRE(grid > 0, "tconv16: %d CUs", g_t16_cus);
+    MVP_REQUIRE(grid > 0, "tconv16: %d CUs", cu_count());
     T16Params p{c.x, c.w_img, c.bias, c.res, c.y, conv_zero_region(), g_t16_sink, c.N, c.Cout, (int)tiles, ncb};
     if (c.res)
         launch_k16<CIN, H, W, TH, NB, BM, true>(p, grid, s);

@@ -263,8 +263,6 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int g_tr_cus = 0;
-
 }  // namespace
 
 bool trans1_supported(int H, int W, int C, int cout0, int cout1) {
@@ -310,15 +308,10 @@ void launch_trans1(const uint16_t* x, const uint16_t* wb, int64_t w0_off, const 
                                     T1C<true>::LDS));
         attr = true;
     }
-    if (g_tr_cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&g_tr_cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     const long tiles = (long)N * (T1C<true>::H / T1C<true>::TH);
     MVP_REQUIRE(tiles * T1C<true>::NCH < (1L << 30), "trans1: too many tiles");
     TrParams p{x, wb, (int)w0_off, (int)w1_off, b0, b1, y0, y1, conv_zero_region(), N, (int)tiles, wimg, planar ? 1 : 0};
-    const int grid = (int)std::min<long>(tiles, g_tr_cus);
+    const int grid = (int)std::min<long>(tiles, cu_count());
     // pixel-major halo (+0.4 % frames/s over plane-major, round 2)
     hipLaunchKernelGGL(trans1_kernel<true>, dim3(grid), dim3(T1C<true>::NTH), T1C<true>::LDS, s, p);
     MVP_HIP(hipGetLastError());

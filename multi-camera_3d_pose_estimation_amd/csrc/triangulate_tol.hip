@@ -509,14 +509,8 @@ void mvp::launch_triangulate_tol2(const float* kpts, int64_t n_points, int V, co
     fb.force = (ff && ff[0] == '1') || out_xyzw != nullptr;
     // 3 f32 + 2 fp64 undistortion iterations: 4 + 1 sends ~0.6 % of the synthetic rigs'
     // points to the exact path (0.013 % with 3 + 2, tools/tri_cert_emu.c)
-    static int cus = 0;  // cached per process, not per device: the first device's count serves all
-    if (cus == 0) {
-        int dev = 0;
-        MVP_HIP(hipGetDevice(&dev));
-        MVP_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    }
     // 5 blocks of 4 waves per CU = the kernel's 5 waves per SIMD (88 VGPRs)
-    const dim3 tgrid((unsigned)std::min<int64_t>(blocks, (int64_t)cus * 5)), block(kBlock);
+    const dim3 tgrid((unsigned)std::min<int64_t>(blocks, (int64_t)cu_count() * 5)), block(kBlock);
     hipLaunchKernelGGL(triangulate_tol2_kernel<3>, tgrid, block, 0, s, kpts, n_points, V, cams, n_cams, ci,
                        out_xyz, out_xyzw, fb);
     hipLaunchKernelGGL(triangulate_tol2_fallback_kernel, dim3(kFbBlocks), block, 0, s, kpts, n_points, V, cams,

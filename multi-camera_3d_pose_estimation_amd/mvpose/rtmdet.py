@@ -1,4 +1,4 @@
-"""RTMDet-m person detector on the libmvpose detector runtime (csrc/detnet.cpp, det.hip).
+"""RTMDet-m person detector on the libmvpose detector runtime (csrc/detnet.cpp, det*.hip).
 
 The reference runs mmdet's RTMDet-m (`detectors.coco_base` in
 examples/model_paths.yaml:2-4: rtmdet_m_640-8xb32_coco-person.py) through
@@ -49,7 +49,7 @@ FEAT = 192
 TEST_CFG = dict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, iou_threshold=0.6, max_per_img=100)
 DET_STEM, DET_CONV, DET_DW, DET_CA, DET_SPP, DET_UP2, DET_HEAD, DET_DWPW = range(8)
 # stored channel counts where the fused dw5 + pw kernel runs (the 160x160 / 80x80 planes: CSPNeXt
-# stages 1-2 and the last top-down block); on the 40x40 / 20x20 planes it measured slower (det.hip)
+# stages 1-2 and the last top-down block); on the 40x40 / 20x20 planes it measured slower (det_dw.hip)
 DWPW_CHANNELS = (64, 96)
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2
 
@@ -345,7 +345,7 @@ class DetSpec:
 
     def dwpw(self, sd, dw_name, pw_name, x: View, out: View, res: View | None = None):
         """DepthwiseSeparableConvModule (5x5 depthwise + BN + SiLU, then 1x1 + BN + SiLU) as ONE
-        op (DET_DWPW, det.hip dwpw_kernel): the depthwise output stays in LDS.  w_off: the
+        op (DET_DWPW, det_dw.hip dwpw_kernel): the depthwise output stays in LDS.  w_off: the
         depthwise f32 weights [C/8][25][8]; b_off: [depthwise bias (C) | pointwise bias (C)] f32;
         aux: the pointwise bf16 weights [C][1][1][C]."""
         wd, bd = fold(sd, dw_name)          # (c, 1, 5, 5)

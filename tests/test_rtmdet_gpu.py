@@ -140,7 +140,7 @@ def test_halo_rows_bitwise(sd, size, n, monkeypatch):
 @pytest.mark.parametrize("size,n", [(128, 3), (640, 2)])
 def test_dwpw_fused_bitwise(sd, size, n, monkeypatch):
     """The CSPNeXt stage-1/2 blocks' conv2 as ONE launch (DET_DWPW: 5x5 depthwise + 1x1 pointwise,
-    the depthwise output kept in LDS; det.hip dwpw_kernel) against the unfused pair (dw5_kernel +
+    the depthwise output kept in LDS; det_dw.hip dwpw_kernel) against the unfused pair (dw5_kernel +
     the 1x1 GEMM, MVPOSE_DET_DWPW=0): the same fma chains, bf16 rounding of the intermediate, MFMA
     operands and K order, so the candidates of every prior and the selected boxes are
     bit-identical (at 128 the 4x4 .. 32x32 planes exercise the partial tiles)."""
