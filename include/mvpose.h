@@ -696,6 +696,94 @@ int mvp_associate_views(const float* kpts_dev, int T, int P, int J, int V, const
                         uint8_t* out_count_dev, double* out_affinity_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Bundle adjustment of the extrinsics over the 2D keypoints: R, T of the cameras that may have
+ * moved since calibration, the 3D points, and a covariance of the camera unknowns.  No reference
+ * counterpart (the reference's extrinsic branch is mvp_sgd_refine_cams: f32, Adam, at most two
+ * learnable cameras, tied to trajectory windows, no uncertainty).
+ *
+ * kpts_dev [n_points][3][V], cams_dev, cam_idx_host / n_cam_idx (2..8) as for
+ * mvp_triangulate_refine: view i reads column cam_idx[i] and the parameters of camera cam_idx[i].
+ * Everything is fp64 with FMA contraction allowed; no atomics on floating-point data, so the same
+ * inputs give the same bits on every call.
+ *   Used view, observation z_i, weight W_i: exactly mvp_triangulate_refine's rules (mask_dev,
+ *     min_conf, the three MVP_REFINE_W_* modes, gauss_dev / J, cov_floor).
+ *   Unknowns: free_mask has bit i set when view i's R, T are optimised; F = popcount(free_mask),
+ *     0 < F <= n_cam_idx - 1 (at least one listed view stays fixed), no bit at or above n_cam_idx.
+ *     The other unknowns are the 3D points.  K and the distortion are never touched.  A free camera
+ *     is perturbed as
+ *       R <- exp([dw]x)·R   (Rodrigues; for |dw| < 1e-12: I + [dw]x)        T <- T + du
+ *     so that for P = R·X + T: dP/d dw = -[P - T]x, dP/d du = I, dP/dX = R.
+ *   Active point: at least 2 used views, a finite seed xyz0, and P_z > 0 in every used view at the
+ *     seed (with the input cameras).  The active set is fixed at the start.  Inactive points take no
+ *     part and return their seed's bits with point status 0x80.  A free view observed by fewer than
+ *     3 active points ends the call at once with info status 3: cameras and points are returned
+ *     unchanged.
+ *   Cost: s² = rᵀ·W·r is the whitened squared residual of one used view, r = pi_i(X) - z_i (the
+ *     forward model of mvp_triangulate_refine).  rho(s) = ½s² when huber_delta <= 0 or s <= delta,
+ *     else delta·(s - ½delta); the IRLS weight is omega = 1 or delta/s, W~ = omega·W.
+ *       f = Σ rho  +  Σ over the free views of ½|T_i - T_i⁰|²/sigma²
+ *     the second sum only when trans_prior_sigma = sigma > 0, T⁰ being the input camera's T.  f is
+ *     +inf when any used view of an active point has P_z <= 0.  With a single fixed camera the
+ *     overall scale of (points, free translations) is unobservable from the pixels: the prior pins
+ *     it, and sigma > 0 is then needed for S to be well conditioned.  With two or more fixed cameras
+ *     their baseline sets the scale, nothing is unobservable, and sigma may be 0.
+ *   Linearisation at a state with damping lambda, per active point p over its used views i:
+ *       J_X = A·R_i (2x3),  J_c = A·[-[P - T]x, I] (2x6, free views),  A = d pixel / dP
+ *       V_p = Σ J_Xᵀ W~ J_X,  g_p = Σ J_Xᵀ W~ r,  W_pi = J_cᵀ W~ J_X (6x3)
+ *       U_i += J_cᵀ W~ J_c,  g_ci += J_cᵀ W~ r
+ *       V*_p = V_p + lambda·diag V_p = L·Lᵀ (Cholesky)
+ *       U*_i = U_i + lambda·diag U_i (+ I/sigma² on the translation block)
+ *       g_ci += (T_i - T_i⁰)/sigma² with the prior
+ *     Reduced system over the 6F camera unknowns, free views in ascending position, each (dw, du):
+ *       S = blockdiag(U*) - Σ_p Y_p·Y_pᵀ,  Y_p = [W_pi·L⁻ᵀ]_i (6F x 3),  b = -g_c + Σ_p Y_p·(L⁻¹ g_p)
+ *     S·dc = b by Cholesky, then dX_p = -V*⁻¹·(g_p + Σ_i W_piᵀ·dc_i).
+ *   Solver: Levenberg-Marquardt, lambda = 1e-3 at the start.  A trial linearises at the current
+ *     state, solves, and forms the trial state (cameras as above, X + dX).  It is accepted when
+ *     f(trial) is finite and <= f: the state becomes the trial state and lambda <- max(lambda/10,
+ *     1e-12); otherwise lambda <- 10·lambda.  A Cholesky pivot that is not > 0 (NaN included) in any
+ *     active point's V* or in S is a rejected trial.  The run stops: converged (status 0) at the
+ *     first accepted trial with f - f(trial) <= tol·f; stalled (status 2) when lambda > 1e12; out
+ *     of trials (status 1) after max_iter trials — tested in this order after each trial.  With
+ *     max_iter = 0 the call returns the seed state with f evaluated there (status 1).
+ *
+ * mvp_bundle_adjust_plan : checks (n_points >= 1, n_cam_idx, free_mask) as the calls do and reports
+ *   the bytes of the caller-owned workspace (contents are scratch) both calls need.
+ * mvp_bundle_adjust_system : ONE linearisation at the given cameras, the given f32 points xyz_dev
+ *   (the active test is made at them) and the given lambda (finite, >= 0); no solve, no state.
+ *   out_S_dev [6F][6F] full symmetric, out_b_dev [6F], out_cost_dev [1] (Σ rho; the prior's cost is
+ *   0 at the input cameras, its I/sigma² is in S), out_counts_dev [2] int64 {active points, used
+ *   views of active points}.  A failed pivot of some V* shows as NaN in S and b.
+ * mvp_bundle_adjust : the whole optimisation, stream-ordered, with no host synchronisation and no
+ *   decision on the host: the number of launches is fixed by max_iter (0..63), and a flag in the
+ *   workspace turns the launches after the end into early returns.
+ *   out_cams_dev [n_cams][MVP_CAM_DOUBLES]: a copy of cams_dev with the free views' R, T replaced
+ *     and their P = K[R|T] recomputed with the loops of mvp_camera_pack.
+ *   out_xyz_dev [n_points][3] float32; out_point_status_dev optional [n_points] uint8 (0 active,
+ *     0x80 inactive).
+ *   out_cam_cov_dev optional [6F][6F] float64: the inverse of S at the final state with lambda = 0
+ *     (the prior's I/sigma² stays in it); NaN when that S, or some point's V, is not positive definite.
+ *   out_info_dev [MVP_BA_INFO_DOUBLES]: f at the seed, f final, trials, accepted trials, status,
+ *     final lambda, active points, used views.
+ * min_conf not NaN; cov_floor >= 0; huber_delta and trans_prior_sigma not NaN (<= 0: off);
+ * tol finite, > 0.  Argument errors return MVP_ERR_ARG before any device work.
+ * ------------------------------------------------------------------------- */
+#define MVP_BA_INFO_DOUBLES 8
+
+int mvp_bundle_adjust_plan(int64_t n_points, int n_cam_idx, unsigned int free_mask, int64_t* workspace_bytes);
+int mvp_bundle_adjust_system(const float* kpts_dev, int64_t n_points, int V, const double* cams_dev, int n_cams,
+                             const int* cam_idx_host, int n_cam_idx, unsigned int free_mask, const float* xyz_dev,
+                             const uint8_t* mask_dev, int weights, const double* gauss_dev, int J, float min_conf,
+                             float cov_floor, double huber_delta, double trans_prior_sigma, double lambda,
+                             void* workspace_dev, int64_t workspace_bytes, double* out_S_dev, double* out_b_dev,
+                             double* out_cost_dev, int64_t* out_counts_dev, void* stream);
+int mvp_bundle_adjust(const float* kpts_dev, int64_t n_points, int V, const double* cams_dev, int n_cams,
+                      const int* cam_idx_host, int n_cam_idx, unsigned int free_mask, const float* xyz0_dev,
+                      const uint8_t* mask_dev, int weights, const double* gauss_dev, int J, float min_conf,
+                      float cov_floor, double huber_delta, double trans_prior_sigma, int max_iter, double tol,
+                      void* workspace_dev, int64_t workspace_bytes, double* out_cams_dev, float* out_xyz_dev,
+                      uint8_t* out_point_status_dev, double* out_cam_cov_dev, double* out_info_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's
  * recordings (utils.py:849-909 read_video_as_frames; synchronize_videos.py:64,240 writes them with
  * cv2.VideoWriter_fourcc(*'mp4v')).  Simple Profile: I / P-VOPs, video packets, H.263 or MPEG

@@ -388,3 +388,113 @@ def associate_views(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[in
          float(trunc_px), float(max_cost_px), int(min_joints), _ptr(work), int(nbytes), _ptr(group), _ptr(count),
          _ptr(aff) if aff is not None else None, _stream(dev))
     return group, count, aff, pairs
+
+
+BA_INFO_FIELDS = ("cost_seed", "cost", "trials", "accepted", "status", "lambda", "active_points", "used_views")
+BA_STATUS = {0: "converged", 1: "out of trials", 2: "stalled", 3: "free view observed by fewer than 3 points"}
+
+
+def _free_mask(free: Sequence[int]) -> int:
+    """View positions (indices into cam_idx) -> the C-ABI's bit mask.  A position that has no bit
+    sets bit 31, which the library refuses by name."""
+    m = 0
+    for i in free:
+        i = int(i)
+        m |= (1 << i) if 0 <= i < 31 else (1 << 31)
+    return m
+
+
+def bundle_adjust_plan(n_points: int, nv: int, free: Sequence[int]) -> int:
+    """Workspace bytes of bundle_adjust / bundle_adjust_system (mvp_bundle_adjust_plan, which
+    refuses what the calls refuse).  free: positions in cam_idx of the views to optimise."""
+    nbytes = ctypes.c_int64(0)
+    call("mvp_bundle_adjust_plan", int(n_points), int(nv), _free_mask(free), ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def _ba_args(kpts, cams, cam_idx, free, xyz, weights, gauss, mask):
+    """Shared front of the two bundle-adjustment calls: checks and the packed arguments."""
+    if weights not in REFINE_WEIGHTS:
+        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
+    nv = len(ci)
+    _require(xyz, torch.float32, "xyz")
+    if tuple(xyz.shape) != lead + (3,):
+        raise ValueError(f"xyz must be {lead + (3,)}, got {tuple(xyz.shape)}")
+    J = 0
+    if weights == "heatmap":
+        if gauss is None:
+            raise ValueError('weights="heatmap" needs gauss, the (T, V, J, 6) float64 heatmap Gaussians')
+        _require(gauss, torch.float64, "gauss")
+        if len(lead) != 2 or tuple(gauss.shape) != (lead[0], V, lead[1], 6):
+            raise ValueError(f"gauss must be (T, V, J, 6) for kpts (T, J, 3, V), got {tuple(gauss.shape)}")
+        J = lead[1]
+    bits = None
+    if mask is not None:
+        _require(mask, torch.bool, "mask")
+        if tuple(mask.shape) != lead + (nv,):
+            raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
+        bits = _pack_view_bits(mask)
+    return V, lead, n, ci, nv, J, bits, _free_mask(free)
+
+
+def bundle_adjust_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], free: Sequence[int],
+                         xyz: torch.Tensor, *, lam: float = 0.0, weights: str = "unit",
+                         gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None, min_conf: float = 0.0,
+                         cov_floor: float = 1.0, huber_delta: float = 0.0, trans_prior_sigma: float = 0.0):
+    """One linearisation of the bundle adjustment (mvp_bundle_adjust_system; stated in
+    include/mvpose.h): the reduced camera system at the given cameras, f32 points and damping.
+
+    kpts, cams, cam_idx, weights, gauss, mask, min_conf, cov_floor as for triangulate_refine; free:
+    positions in cam_idx of the views whose R, T are unknowns (F of them, at least one view stays
+    fixed).  Returns (S (6F, 6F) float64, b (6F,) float64, cost () float64, counts (2,) int64:
+    active points and their used views), all on the GPU."""
+    V, lead, n, ci, nv, J, bits, fm = _ba_args(kpts, cams, cam_idx, free, xyz, weights, gauss, mask)
+    nbytes = ctypes.c_int64(0)
+    call("mvp_bundle_adjust_plan", n, nv, fm, ctypes.byref(nbytes))
+    dev = kpts.device
+    n6 = 6 * bin(fm).count("1")
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    S = torch.empty((n6, n6), dtype=torch.float64, device=dev)
+    b = torch.empty((n6,), dtype=torch.float64, device=dev)
+    cost = torch.empty((), dtype=torch.float64, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    call("mvp_bundle_adjust_system", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, fm, _ptr(xyz),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor),
+         float(huber_delta), float(trans_prior_sigma), float(lam), _ptr(work), nbytes.value, _ptr(S), _ptr(b),
+         _ptr(cost), _ptr(counts), _stream(dev))
+    return S, b, cost, counts
+
+
+def bundle_adjust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], free: Sequence[int],
+                  xyz0: torch.Tensor, *, weights: str = "unit", gauss: torch.Tensor | None = None,
+                  mask: torch.Tensor | None = None, min_conf: float = 0.0, cov_floor: float = 1.0,
+                  huber_delta: float = 0.0, trans_prior_sigma: float = 0.0, max_iter: int = 30, tol: float = 1e-6):
+    """Bundle adjustment of the free views' R, T and the 3D points over the 2D keypoints
+    (mvp_bundle_adjust; the problem and the solver are stated in include/mvpose.h).
+
+    Arguments as for bundle_adjust_system, xyz0 (..., 3) float32 being the seed.  Levenberg-Marquardt,
+    at most max_iter trials, converged at an accepted cost decrease <= tol·cost; with a single fixed
+    view trans_prior_sigma > 0 (world units) is what pins the scale.  Stream-ordered, no host
+    synchronisation.  Returns (cams (n_cams, 40) float64: the input with the free views' R, T and P
+    replaced; xyz (..., 3) float32; point_status (...) uint8: 0x80 for a point that took no part
+    and is returned as its seed; cam_cov (6F, 6F) float64 over (dw, du) per free view in ascending
+    position; info (8,) float64: BA_INFO_FIELDS), all on the GPU."""
+    V, lead, n, ci, nv, J, bits, fm = _ba_args(kpts, cams, cam_idx, free, xyz0, weights, gauss, mask)
+    nbytes = ctypes.c_int64(0)
+    call("mvp_bundle_adjust_plan", n, nv, fm, ctypes.byref(nbytes))
+    dev = kpts.device
+    n6 = 6 * bin(fm).count("1")
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    out_cams = torch.empty_like(cams)
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
+    status = torch.empty(lead, dtype=torch.uint8, device=dev)
+    cov = torch.empty((n6, n6), dtype=torch.float64, device=dev)
+    info = torch.empty((8,), dtype=torch.float64, device=dev)
+    call("mvp_bundle_adjust", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, fm, _ptr(xyz0),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor),
+         float(huber_delta), float(trans_prior_sigma), int(max_iter), float(tol), _ptr(work), nbytes.value,
+         _ptr(out_cams), _ptr(out), _ptr(status), _ptr(cov), _ptr(info), _stream(dev))
+    return out_cams, out, status, cov, info
