@@ -336,8 +336,8 @@ int mvp_graph_destroy(void* handle);
 /* Diagnostics (no reference counterpart): the kernel launches one mvp_graph_forward of `batch`
  * crops issues, in order, as records of 4 int64 {launching op, route, crops, MACs of every op
  * the launch covers}; route 1 fused BasicBlock, 2 transition twin, 3 s2 siblings, 4 head +
- * fuse, 5 Bottleneck, 6 stem pair, 7 stem, 8 conv, 9 1x1 pair, 10 fuse sum.  Fails unless every
- * op is covered by exactly one launch.  *covered_macs_out (optional) = the sum.
+ * fuse, 5 Bottleneck, 6 stem pair, 7 stem, 8 conv, 9 1x1 pair, 10 fuse sum.  Every op is covered
+ * by exactly one launch (mvp_graph_create checks it).  *covered_macs_out (optional) = the sum.
  * tools/fwd_breakdown.py pairs the records with a kernel trace. */
 int mvp_graph_plan(void* handle, int batch, int64_t* rec_out, int max_records, int* n_records,
                    int64_t* covered_macs_out);

@@ -1,5 +1,5 @@
 // Internal (not part of the C-ABI): convolution / fuse launchers used by the
-// HRNet graph runtime (hrnet.cpp).
+// HRNet graph runtime (graph.cpp).
 #pragma once
 #include <cstdlib>
 #include <hip/hip_runtime.h>

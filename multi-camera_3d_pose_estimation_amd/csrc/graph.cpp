@@ -1,4 +1,5 @@
-// Backbone graph runtime: validation, liveness-based arena planning, launch.
+// Backbone graph runtime: validation, fusion passes that compile the ops into one launch
+// list, liveness-based arena planning from that list, launch.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -10,8 +11,48 @@
 namespace mvp {
 namespace {
 
+// The kernel a launch runs; the numbers are mvp_graph_plan's documented route values.
+enum Route {
+    R_BLOCK = 1,      // fused BasicBlock (op - 1, op)
+    R_TWIN = 2,       // transition1: 3x3/s1 conv + its 3x3/s2 twin
+    R_SIBLINGS = 3,   // 3x3/s2 siblings on one input
+    R_HEAD_FUSE = 4,  // heatmap head + the last fuse sum
+    R_BNECK = 5,      // whole Bottleneck
+    R_STEM2 = 6,      // stem conv + conv2
+    R_STEM = 7,
+    R_CONV = 8,       // one conv (possibly cat-fused)
+    R_PAIR = 9,       // Bottleneck join: 1x1 conv (possibly cat-fused) + the next block's conv1
+    R_FUSE_SUM = 10,
+};
+
+// One kernel launch of the forward.  The fusion passes emit these; arena planning, forward,
+// mvp_graph_plan and the derived-weight fill only read them.
+struct Launch {
+    Route route;
+    int op;                     // launching op: the launch's place in op order (plan records, lifetimes)
+    std::vector<int> covers;    // every op it computes, launcher first (R_SIBLINGS: in output order)
+    std::vector<int> reads;     // tensors it reads from memory ...
+    std::vector<int> writes;    // ... and writes to it; LDS / register intermediates are in neither
+    int64_t macs = 0;           // per crop, over covers
+    // route parameters (op indices, -1: none)
+    int cat_src = -1;           // R_CONV / R_PAIR / lead R_BNECK: absorbed 1x1 whose input and weights are concatenated
+    int tail = -1;              // R_PAIR: the 256 -> 64 successor
+    int conv1 = -1, conv2 = -1; // R_BNECK
+    int perm = 0;               // R_BNECK: conv1 sums K in the Bottleneck join's order (bneck.hip)
+    int lead = 0;               // R_BNECK: layer1's first block, 64-ch input, conv3 cat-fused with the downsample
+    int stem = -1;              // R_STEM2
+    int twin = -1;              // R_TWIN
+    int fuse = -1;              // R_HEAD_FUSE
+    int planar = 0;             // R_BNECK output / R_TWIN input in chunk-planar layout
+    // derived weights (owned; alloc_weights / fill_weights / free_weights)
+    uint16_t* w = nullptr;      // cat_src: [cout_pad][cin + cin_src]; R_SIBLINGS: [128][3][3][cin]
+    float* b = nullptr;         // cat_src: summed biases [cout_pad]; R_SIBLINGS: [128]
+    uint16_t* w_img = nullptr;  // R_CONV: tconv16 image; R_TWIN: trans1 image
+};
+
 struct Segment {
     int first_op = 0, last_op = -1;  // inclusive op range
+    int first_launch = 0, end_launch = 0;
     int micro_batch = 0;             // 0 = whole batch
 };
 
@@ -24,26 +65,9 @@ struct Graph {
     const uint16_t* wb = nullptr;
     const float* fb = nullptr;
     int max_batch = 0;
-    std::vector<int> absorbed;    // op folded into another op (fused BasicBlock / cat-fusion), not run on its own
-    std::vector<int> block_head;  // op runs the fused BasicBlock of (op - 1, op)
-    std::vector<int> cat_src;     // 1x1 op that also computes the absorbed 1x1 op cat_src[k] (-1: none)
-    std::vector<uint16_t*> cat_w; // its concatenated weights [cout_pad][cin_k + cin_src] (owned)
-    std::vector<float*> cat_b;    // and summed biases [cout_pad] (owned)
-    std::vector<int> pair_tail;   // 1x1 op whose 256->64 successor (absorbed) runs in the same launch (-1: none)
-    std::vector<int> stem_head;   // 3x3/s2 conv that also runs the (absorbed) stem op stem_head[k] (-1: none)
-    std::vector<int> twin;        // 3x3/s1 conv whose (absorbed) 3x3/s2 sibling on the same input runs in its launch
-    std::vector<std::vector<int>> sib;  // 3x3/s2 conv whose (absorbed) 3x3/s2 siblings on its input run in its launch
-    std::vector<uint16_t*> sib_w;       // their cout-concatenated weights [128][3][3][cin] (owned)
-    std::vector<float*> sib_b;          // and biases [128] (owned)
-    std::vector<uint16_t*> t16_w;       // tconv16 weight image of a 128/256-ch branch-plane conv (owned)
-    std::vector<uint16_t*> tr_w;        // trans1 weight image of a twin-fused transition (owned)
-    std::vector<int> head_src;          // heatmap head that also runs the (absorbed) fuse op head_src[k] (-1: none)
-    std::vector<int> bneck;             // Bottleneck conv3 whose (absorbed) conv1 bneck[k] and conv2 run in its launch (-1: none)
-    std::vector<int> bneck_mid;         // and its (absorbed) conv2
-    std::vector<int> bneck_perm;        // its conv1 sums K in the Bottleneck join's order (bneck.hip)
-    std::vector<int> bneck_lead;        // layer1's first block: 64-ch input, conv3 cat-fused with the downsample
-    std::vector<int> planar;            // bneck head / trans1 twin: its output / input in chunk-planar layout
-    std::vector<int64_t> offset;  // per-crop-batch arena offsets (bytes), -1 = external
+    std::vector<Launch> launches;  // in op order once finish_launches has run
+    std::vector<int> owner;        // per op: index of the launch that covers it, -1 = none yet
+    std::vector<int64_t> offset;   // per-crop-batch arena offsets (bytes), -1 = external
     int64_t arena_bytes = 0;
     char* arena = nullptr;
 };
@@ -52,6 +76,11 @@ int64_t elem_size(int dtype) { return dtype == MVP_DT_F32_NCHW ? 4 : 2; }
 
 int64_t tensor_bytes(const mvp_tensor_desc& t, int batch) {
     return (int64_t)batch * t.h * t.w * t.c * elem_size(t.dtype);
+}
+
+bool env_set(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '1';
 }
 
 void validate(Graph& g, int64_t w_elems, int64_t f_elems) {
@@ -127,296 +156,266 @@ void validate(Graph& g, int64_t w_elems, int64_t f_elems) {
     }
 }
 
-// Fusion pass: a 3x3 conv pair conv1 (relu) -> conv2 (+ conv1's input as residual,
-// relu) on 32 channels (64x48 plane) or 64 channels (32x24 plane, tblock64.hip) whose
-// intermediate feeds nothing else becomes one fused BasicBlock launch; the intermediate
-// tensor is then never allocated.
-void fuse(Graph& g, bool enable) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.absorbed.assign(no, 0);
-    g.block_head.assign(no, 0);
-    if (!enable) return;
-    std::vector<int> uses(nt, 0);
-    for (const mvp_op_desc& op : g.ops)
+// ---- what the fusion passes share ----------------------------------------------------------
+
+bool is_free(const Graph& g, int k) { return k >= 0 && g.owner[k] < 0; }
+
+// The launch op k launches itself (nullptr: k is free, or absorbed into another op's launch).
+Launch* launch_of(Graph& g, int k) {
+    if (k < 0 || g.owner[k] < 0) return nullptr;
+    Launch& L = g.launches[g.owner[k]];
+    return L.op == k ? &L : nullptr;
+}
+
+void cover(Graph& g, Launch& L, int k) {
+    L.covers.push_back(k);
+    g.owner[k] = (int)(&L - g.launches.data());
+}
+
+Launch& emit(Graph& g, Route route, int op, std::vector<int> reads, std::vector<int> writes) {
+    g.launches.push_back(Launch{route, op, {}, std::move(reads), std::move(writes)});
+    cover(g, g.launches.back(), op);
+    return g.launches.back();
+}
+
+bool has_res(const mvp_op_desc& op) { return op.n_in > 1 && op.in[1] >= 0; }
+
+// A conv of this kernel size, stride and activation (relu < 0: either) with a bf16 NHWC output ...
+bool is_conv(const Graph& g, int k, int ks, int stride, int relu) {
+    if (k < 0) return false;
+    const mvp_op_desc& op = g.ops[k];
+    return op.kind == MVP_OP_CONV && op.ks == ks && op.stride == stride && (relu < 0 || !op.relu == !relu) &&
+           g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
+}
+// ... and no residual.
+bool plain_conv(const Graph& g, int k, int ks, int stride, int relu) {
+    return is_conv(g, k, ks, stride, relu) && !has_res(g.ops[k]);
+}
+
+// The launch of a conv on its own: reads its input and residual, writes its output.
+Launch& emit_conv(Graph& g, int k) {
+    const mvp_op_desc& op = g.ops[k];
+    std::vector<int> reads{op.in[0]};
+    if (has_res(op)) reads.push_back(op.in[1]);
+    return emit(g, R_CONV, k, reads, {op.out});
+}
+
+// Readers per tensor and producing op per tensor.  skip_block_mid: a fused BasicBlock's
+// intermediate (its head's in[0]) is not counted as read.
+struct UseDef {
+    std::vector<int> uses, producer;
+};
+UseDef use_def(Graph& g, bool skip_block_mid) {
+    const int nt = (int)g.tensors.size();
+    UseDef ud{std::vector<int>(nt, 0), std::vector<int>(nt, -1)};
+    for (int k = 0; k < (int)g.ops.size(); k++) {
+        const mvp_op_desc& op = g.ops[k];
+        ud.producer[op.out] = k;
+        const Launch* L = skip_block_mid ? launch_of(g, k) : nullptr;
         for (int i = 0; i < op.n_in; i++)
-            if (op.in[i] >= 0) uses[op.in[i]]++;
-    auto is_block_conv3 = [&](const mvp_op_desc& op) {
-        return op.kind == MVP_OP_CONV && op.ks == 3 && op.stride == 1 && (op.cin == 32 || op.cin == 64) &&
-               op.cout == op.cin && op.relu && g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
+            if (op.in[i] >= 0 && !(i == 0 && L && L->route == R_BLOCK)) ud.uses[op.in[i]]++;
+    }
+    return ud;
+}
+
+// Input channels of a 1x1 launch: its op's, plus the cat-fused source's.
+int cat_cin(Graph& g, int k) {
+    const Launch* L = launch_of(g, k);
+    return g.ops[k].cin + (L && L->cat_src >= 0 ? g.ops[L->cat_src].cin : 0);
+}
+
+// ---- fusion passes, in the order mvp_graph_create runs them ---------------------------------
+
+// A 3x3 conv pair conv1 (relu) -> conv2 (+ conv1's input as residual, relu) on 32 channels
+// (64x48 plane) or 64 channels (32x24 plane, tblock64.hip) whose intermediate feeds nothing
+// else becomes one fused BasicBlock launch; the intermediate tensor is then never allocated.
+void fuse(Graph& g) {
+    const int no = (int)g.ops.size();
+    const UseDef ud = use_def(g, false);
+    auto is_block_conv3 = [&](int k) {
+        const mvp_op_desc& op = g.ops[k];
+        return is_conv(g, k, 3, 1, 1) && (op.cin == 32 || op.cin == 64) && op.cout == op.cin;
     };
     for (int k = 0; k + 1 < no; k++) {
         const mvp_op_desc& a = g.ops[k];
         const mvp_op_desc& b = g.ops[k + 1];
-        if (g.absorbed[k] || g.block_head[k] || !is_block_conv3(a) || !is_block_conv3(b) || a.cin != b.cin) continue;
-        const bool a_plain = a.n_in == 1 || a.in[1] < 0;
+        if (!is_free(g, k) || !is_block_conv3(k) || !is_block_conv3(k + 1) || a.cin != b.cin) continue;
         const bool b_res = b.n_in > 1 && b.in[1] == a.in[0];
         const mvp_tensor_desc& t = g.tensors[a.out];
-        if (!a_plain || !b_res || b.in[0] != a.out || uses[a.out] != 1 || a.out == g.output) continue;
+        if (has_res(a) || !b_res || b.in[0] != a.out || ud.uses[a.out] != 1 || a.out == g.output) continue;
         const bool ok = a.cin == 32 ? basic_block_c32_supported(t.h, t.w) : tblock64_supported(t.h, t.w);
         if (a.segment != b.segment || !ok) continue;
-        g.absorbed[k] = 1;
-        g.block_head[k + 1] = 1;
+        cover(g, emit(g, R_BLOCK, k + 1, {a.in[0]}, {b.out}), k);
         k++;
     }
 }
 
-// Cat-fusion pass: y = act(conv1x1_B(h) + bias_B + t) whose residual t = conv1x1_A(x) + bias_A
+// Cat-fusion: y = act(conv1x1_B(h) + bias_B + t) whose residual t = conv1x1_A(x) + bias_A
 // (no activation, consumed only here: the Bottleneck downsample) becomes ONE 1x1 conv over
 // the channel concatenation [h, x] with weights [W_B | W_A] and bias bias_B + bias_A.  The
 // t tensor (256 channels at 64x48 in HRNet-W32: 1.6 GB per 1024 crops, written then read
 // back as the residual) disappears, and t is no longer rounded to bf16 before the add.
-void cat_fuse(Graph& g, bool enable) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.cat_src.assign(no, -1);
-    g.cat_w.assign(no, nullptr);
-    g.cat_b.assign(no, nullptr);
-    if (!enable) return;
-    std::vector<int> uses(nt, 0), producer(nt, -1);
-    for (int k = 0; k < no; k++) {
-        const mvp_op_desc& op = g.ops[k];
-        producer[op.out] = k;
-        for (int i = 0; i < op.n_in; i++)
-            if (op.in[i] >= 0 && !(g.block_head[k] && i == 0)) uses[op.in[i]]++;
-    }
-    auto plain_1x1 = [&](const mvp_op_desc& op) {
-        return op.kind == MVP_OP_CONV && op.ks == 1 && op.stride == 1 && op.cin % 32 == 0 &&
-               g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
-    };
-    for (int b = 0; b < no; b++) {
+void cat_fuse(Graph& g) {
+    const UseDef ud = use_def(g, true);
+    for (int b = 0; b < (int)g.ops.size(); b++) {
         const mvp_op_desc& B = g.ops[b];
-        if (g.absorbed[b] || g.block_head[b] || !plain_1x1(B) || B.n_in < 2 || B.in[1] < 0) continue;
-        const int t = B.in[1], a = producer[t];
-        if (a < 0 || a >= b || g.absorbed[a] || g.block_head[a] || g.cat_src[a] >= 0) continue;
+        if (!is_free(g, b) || !is_conv(g, b, 1, 1, -1) || !has_res(B)) continue;
+        const int t = B.in[1], a = ud.producer[t];
+        if (a >= b || !is_free(g, a) || !plain_conv(g, a, 1, 1, 0)) continue;
         const mvp_op_desc& A = g.ops[a];
-        if (!plain_1x1(A) || (A.n_in > 1 && A.in[1] >= 0) || A.relu || A.cout != B.cout) continue;
-        if (uses[t] != 1 || t == g.output || A.segment != B.segment) continue;
+        if (A.cout != B.cout || ud.uses[t] != 1 || t == g.output || A.segment != B.segment) continue;
         const int kch = (A.cin + B.cin) / 32;  // conv1x1_kernel instantiations: K = 32, 64, 128, 256
         if (kch != 2 && kch != 4 && kch != 8) continue;
-        g.absorbed[a] = 1;
-        g.cat_src[b] = a;
+        Launch& L = emit(g, R_CONV, b, {B.in[0], A.in[0]}, {B.out});
+        L.cat_src = a;
+        cover(g, L, a);
     }
 }
 
-// Pair-fusion pass (Bottleneck join): a 1x1 conv A producing 256 channels with ReLU (the
-// Bottleneck's conv3, single input + residual or cat-fused with the downsample) whose
-// output T is read by a 1x1 conv B (256 -> 64, ReLU, no residual: the next Bottleneck's
-// conv1) runs as one conv1x1_pair launch that writes T (still needed as the next
-// residual) and B's output; T is no longer re-read for B.
-void pair_fuse(Graph& g, bool enable) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.pair_tail.assign(no, -1);
-    if (!enable) return;
-    std::vector<int> producer(nt, -1);
-    for (int k = 0; k < no; k++) producer[g.ops[k].out] = k;
-    auto plain_1x1 = [&](int k) {
-        const mvp_op_desc& op = g.ops[k];
-        return !g.absorbed[k] && !g.block_head[k] && g.bneck[k] < 0 && op.kind == MVP_OP_CONV && op.ks == 1 &&
-               op.stride == 1 &&
-               op.relu && g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
+// The Bottleneck chain ending in conv3 c (1x1 64 -> 256): conv1 a (1x1 cin1 -> 64) -> conv2 b
+// (3x3 64 -> 64) -> c, all ReLU, a and b free with no residual and outputs nothing else reads,
+// one segment, on the plane bneck.hip serves.
+bool bneck_chain(Graph& g, const UseDef& ud, int c, int cin1, int& a, int& b) {
+    auto mid = [&](int k, int ks, int cin) {
+        return is_free(g, k) && plain_conv(g, k, ks, 1, 1) && g.ops[k].cin == cin && g.ops[k].cout == 64 &&
+               ud.uses[g.ops[k].out] == 1 && g.ops[k].out != g.output && g.ops[k].segment == g.ops[c].segment;
     };
-    for (int b = 0; b < no; b++) {
-        const mvp_op_desc& B = g.ops[b];
-        if (!plain_1x1(b) || (B.n_in > 1 && B.in[1] >= 0) || B.cin != 256 || B.cout != 64) continue;
-        const int a = producer[B.in[0]];
-        if (a < 0 || a >= b || !plain_1x1(a) || g.pair_tail[a] >= 0) continue;
-        const mvp_op_desc& A = g.ops[a];
-        const int cin = A.cin + (g.cat_src[a] >= 0 ? g.ops[g.cat_src[a]].cin : 0);
-        if (A.cout != 256 || A.segment != B.segment) continue;
-        if (!conv1x1_pair_supported(cin, A.cout, B.cout)) continue;
-        g.pair_tail[a] = b;
-        g.absorbed[b] = 1;
-    }
+    if (!is_conv(g, c, 1, 1, 1) || g.ops[c].cin != 64 || g.ops[c].cout != 256) return false;
+    b = ud.producer[g.ops[c].in[0]];
+    if (!mid(b, 3, 64)) return false;
+    a = ud.producer[g.ops[b].in[0]];
+    if (!mid(a, 1, cin1)) return false;
+    const mvp_tensor_desc& x = g.tensors[g.ops[a].in[0]];
+    return bneck_supported(x.h, x.w, x.c, g.ops[a].cout);
 }
 
-// Bottleneck-fusion pass (bneck.hip): layer1's Bottleneck on the 256-ch 64x48 plane — conv1
-// (1x1 256 -> 64, ReLU), conv2 (3x3 64 -> 64, ReLU), conv3 (1x1 64 -> 256, + the block's
-// input, ReLU), intermediates read by nothing else — runs as one streaming launch; the two
-// 64-ch intermediates are never allocated.  Runs before pair_fuse (which would otherwise join
-// conv1 to the previous block's conv3); conv1 keeps the K order the join would have given it
-// (bneck_perm) so the result stays bit-identical to the unfused graph.
-void bneck_fuse(Graph& g, bool enable, bool pair_enabled) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.bneck.assign(no, -1);
-    g.bneck_mid.assign(no, -1);
-    g.bneck_perm.assign(no, 0);
-    g.bneck_lead.assign(no, 0);
-    if (!enable) return;
-    std::vector<int> uses(nt, 0), producer(nt, -1);
-    for (int k = 0; k < no; k++) {
-        const mvp_op_desc& op = g.ops[k];
-        producer[op.out] = k;
-        for (int i = 0; i < op.n_in; i++)
-            if (op.in[i] >= 0 && !(g.block_head[k] && i == 0)) uses[op.in[i]]++;
-    }
-    auto conv = [&](int k, int ks, int cin, int cout) {
-        if (k < 0 || g.absorbed[k] || g.block_head[k] || g.cat_src[k] >= 0) return false;
-        const mvp_op_desc& op = g.ops[k];
-        return op.kind == MVP_OP_CONV && op.ks == ks && op.stride == 1 && op.relu && op.cin == cin &&
-               op.cout == cout && g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
-    };
-    auto no_res = [&](int k) { return g.ops[k].n_in < 2 || g.ops[k].in[1] < 0; };
+// Bottleneck fusion (bneck.hip): layer1's Bottleneck on the 256-ch 64x48 plane — conv1 (1x1
+// 256 -> 64, ReLU), conv2 (3x3 64 -> 64, ReLU), conv3 (1x1 64 -> 256, + the block's input,
+// ReLU), intermediates read by nothing else — runs as one streaming launch; the two 64-ch
+// intermediates are never allocated.  Runs before pair_fuse (which would otherwise join conv1
+// to the previous block's conv3); conv1 keeps the K order the join would have given it (perm)
+// so the result stays bit-identical to the unfused graph.
+void bneck_fuse(Graph& g, bool pair_enabled) {
+    const int no = (int)g.ops.size();
+    const UseDef ud = use_def(g, true);
+    int a = -1, b = -1;
     for (int c = 0; c < no; c++) {
-        if (!conv(c, 1, 64, 256) || no_res(c)) continue;
         const mvp_op_desc& C = g.ops[c];
-        const int b = producer[C.in[0]];
-        if (!conv(b, 3, 64, 64) || !no_res(b) || uses[g.ops[b].out] != 1) continue;
-        const int a = producer[g.ops[b].in[0]];
-        if (!conv(a, 1, 256, 64) || !no_res(a) || uses[g.ops[a].out] != 1) continue;
-        const mvp_op_desc& A = g.ops[a];
-        if (A.in[0] != C.in[1] || A.segment != C.segment || g.ops[b].segment != C.segment) continue;
-        if (g.ops[b].out == g.output || A.out == g.output) continue;
-        const mvp_tensor_desc& x = g.tensors[A.in[0]];
-        if (!bneck_supported(x.h, x.w, x.c, A.cout)) continue;
+        if (!is_free(g, c) || !has_res(C) || !bneck_chain(g, ud, c, 256, a, b) || g.ops[a].in[0] != C.in[1]) continue;
         // would pair_fuse have joined conv1 to its producer (a 1x1 256-cout ReLU conv)?
-        int perm = 0;
-        const int f = producer[A.in[0]];
-        if (pair_enabled && f >= 0 && !g.absorbed[f] && !g.block_head[f]) {
-            const mvp_op_desc& F = g.ops[f];
-            const int cin = F.cin + (g.cat_src[f] >= 0 ? g.ops[g.cat_src[f]].cin : 0);
-            perm = F.kind == MVP_OP_CONV && F.ks == 1 && F.stride == 1 && F.relu && F.cout == 256 &&
-                   F.segment == A.segment && g.tensors[F.out].dtype == MVP_DT_BF16_NHWC &&
-                   conv1x1_pair_supported(cin, 256, 64);
-        }
-        g.absorbed[a] = 1;
-        g.absorbed[b] = 1;
-        g.bneck[c] = a;
-        g.bneck_mid[c] = b;
-        g.bneck_perm[c] = perm;
+        const int f = ud.producer[C.in[1]];
+        const bool perm = pair_enabled && f >= 0 && (is_free(g, f) || launch_of(g, f)) && is_conv(g, f, 1, 1, 1) &&
+                          g.ops[f].cout == 256 && g.ops[f].segment == C.segment &&
+                          conv1x1_pair_supported(cat_cin(g, f), 256, 64);
+        Launch& L = emit(g, R_BNECK, c, {C.in[1]}, {C.out});
+        L.conv1 = a, L.conv2 = b, L.perm = perm;
+        cover(g, L, a);
+        cover(g, L, b);
     }
     // layer1's first block: conv1 (1x1 64 -> 64) and the downsample (1x1 64 -> 256, cat-fused
     // into conv3) read the same 64-ch tensor; conv3's K is [conv2's output | that tensor]
     for (int c = 0; c < no; c++) {
-        const int d = g.cat_src[c];
-        if (d < 0 || g.absorbed[c] || g.block_head[c] || g.bneck[c] >= 0) continue;
-        const mvp_op_desc& C = g.ops[c];
-        if (C.kind != MVP_OP_CONV || C.ks != 1 || C.stride != 1 || !C.relu || C.cin != 64 || C.cout != 256 ||
-            g.tensors[C.out].dtype != MVP_DT_BF16_NHWC || g.ops[d].cin != 64)
-            continue;
-        const int b = producer[C.in[0]];
-        if (b < 0 || g.absorbed[b] || g.block_head[b] || g.cat_src[b] >= 0) continue;
-        const mvp_op_desc& B = g.ops[b];
-        if (B.kind != MVP_OP_CONV || B.ks != 3 || B.stride != 1 || !B.relu || B.cin != 64 || B.cout != 64 ||
-            !no_res(b) || uses[B.out] != 1 || B.out == g.output)
-            continue;
-        const int a = producer[B.in[0]];
-        if (a < 0 || g.absorbed[a] || g.block_head[a] || g.cat_src[a] >= 0) continue;
-        const mvp_op_desc& A = g.ops[a];
-        if (A.kind != MVP_OP_CONV || A.ks != 1 || A.stride != 1 || !A.relu || A.cin != 64 || A.cout != 64 ||
-            !no_res(a) || uses[A.out] != 1 || A.out == g.output || A.in[0] != g.ops[d].in[0])
-            continue;
-        if (A.segment != C.segment || B.segment != C.segment) continue;
-        const mvp_tensor_desc& x = g.tensors[A.in[0]];
-        if (!bneck_supported(x.h, x.w, x.c, A.cout)) continue;
-        g.absorbed[a] = 1;
-        g.absorbed[b] = 1;
-        g.bneck[c] = a;
-        g.bneck_mid[c] = b;
-        g.bneck_lead[c] = 1;
+        Launch* L = launch_of(g, c);
+        if (!L || L->route != R_CONV || L->cat_src < 0) continue;
+        const mvp_op_desc& D = g.ops[L->cat_src];
+        if (D.cin != 64 || !bneck_chain(g, ud, c, 64, a, b) || g.ops[a].in[0] != D.in[0]) continue;
+        L->route = R_BNECK;
+        L->reads = {D.in[0]};
+        L->conv1 = a, L->conv2 = b, L->lead = 1;
+        cover(g, *L, a);
+        cover(g, *L, b);
     }
 }
 
-// Stem-fusion pass: the stem conv (OP_STEM, 4 -> 64, s2) whose output feeds only a
-// 3x3/s2 64 -> 64 conv (HRNet's conv2) runs inside that conv's launch (stem2.hip); the
-// 128x96x64 intermediate (1.6 GB per 1024 crops) is never allocated.
-void stem_fuse(Graph& g, bool enable) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.stem_head.assign(no, -1);
-    if (!enable) return;
-    std::vector<int> uses(nt, 0);
-    for (const mvp_op_desc& op : g.ops)
-        for (int i = 0; i < op.n_in; i++)
-            if (op.in[i] >= 0) uses[op.in[i]]++;
+// Pair fusion (Bottleneck join): a 1x1 conv A producing 256 channels with ReLU (the
+// Bottleneck's conv3, single input + residual or cat-fused with the downsample) whose
+// output T is read by a 1x1 conv B (256 -> 64, ReLU, no residual: the next Bottleneck's
+// conv1) runs as one conv1x1_pair launch that writes T (still needed as the next
+// residual) and B's output; T is no longer re-read for B.
+void pair_fuse(Graph& g) {
+    const UseDef ud = use_def(g, false);
+    for (int b = 0; b < (int)g.ops.size(); b++) {
+        const mvp_op_desc& B = g.ops[b];
+        if (!is_free(g, b) || !plain_conv(g, b, 1, 1, 1) || B.cin != 256 || B.cout != 64) continue;
+        const int a = ud.producer[B.in[0]];
+        Launch* L = launch_of(g, a);
+        if (a < 0 || a >= b || !(is_free(g, a) || (L && L->route == R_CONV)) || !is_conv(g, a, 1, 1, 1)) continue;
+        const mvp_op_desc& A = g.ops[a];
+        if (A.cout != 256 || A.segment != B.segment) continue;
+        if (!conv1x1_pair_supported(cat_cin(g, a), A.cout, B.cout)) continue;
+        if (!L) L = &emit_conv(g, a);
+        L->route = R_PAIR;
+        L->tail = b;
+        L->writes.push_back(B.out);
+        cover(g, *L, b);
+    }
+}
+
+// Stem fusion: the stem conv (OP_STEM, 4 -> 64, s2) whose output feeds only a 3x3/s2 64 -> 64
+// conv (HRNet's conv2) runs inside that conv's launch (stem2.hip); the 128x96x64 intermediate
+// (1.6 GB per 1024 crops) is never allocated.
+void stem_fuse(Graph& g) {
+    const int no = (int)g.ops.size();
+    const UseDef ud = use_def(g, false);
     for (int a = 0; a < no; a++) {
         const mvp_op_desc& A = g.ops[a];
-        if (A.kind != MVP_OP_STEM || g.absorbed[a] || uses[A.out] != 1 || A.out == g.output) continue;
+        if (A.kind != MVP_OP_STEM || !is_free(g, a) || ud.uses[A.out] != 1 || A.out == g.output) continue;
         for (int b = a + 1; b < no; b++) {
             const mvp_op_desc& B = g.ops[b];
             if (B.in[0] != A.out) continue;
             const mvp_tensor_desc& x = g.tensors[A.in[0]];
-            if (B.kind == MVP_OP_CONV && !g.absorbed[b] && !g.block_head[b] && g.cat_src[b] < 0 &&
-                g.pair_tail[b] < 0 && B.ks == 3 && B.stride == 2 && B.relu && (B.n_in < 2 || B.in[1] < 0) &&
-                B.segment == A.segment && g.tensors[B.out].dtype == MVP_DT_BF16_NHWC &&
+            if (is_free(g, b) && plain_conv(g, b, 3, 2, 1) && B.segment == A.segment &&
                 stem2_supported(x.h, x.w, B.cin, B.cout)) {
-                g.absorbed[a] = 1;
-                g.stem_head[b] = a;
+                Launch& L = emit(g, R_STEM2, b, {A.in[0]}, {B.out});
+                L.stem = a;
+                cover(g, L, a);
             }
             break;
         }
     }
 }
 
-// Transition-fusion pass: HRNet's transition1 reads the layer1 output (256 ch @ 64x48) with
-// two 3x3 convs (s1 -> 32 ch, s2 -> 64 ch); trans1.hip runs both from one pass over it.
-void twin_fuse(Graph& g, bool enable) {
+// Transition fusion: HRNet's transition1 reads the layer1 output (256 ch @ 64x48) with two
+// 3x3 convs (s1 -> 32 ch, s2 -> 64 ch); trans1.hip runs both from one pass over it.
+void twin_fuse(Graph& g) {
     const int no = (int)g.ops.size();
-    g.twin.assign(no, -1);
-    if (!enable) return;
-    auto plain3 = [&](int k, int stride) {
-        const mvp_op_desc& op = g.ops[k];
-        return op.kind == MVP_OP_CONV && !g.absorbed[k] && !g.block_head[k] && g.cat_src[k] < 0 &&
-               g.pair_tail[k] < 0 && g.stem_head[k] < 0 && op.ks == 3 && op.stride == stride && op.relu &&
-               (op.n_in < 2 || op.in[1] < 0) && g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
-    };
     for (int a = 0; a < no; a++) {
-        if (!plain3(a, 1)) continue;
+        if (!is_free(g, a) || !plain_conv(g, a, 3, 1, 1)) continue;
         const mvp_op_desc& A = g.ops[a];
         const mvp_tensor_desc& x = g.tensors[A.in[0]];
         for (int b = a + 1; b < no; b++) {
             const mvp_op_desc& B = g.ops[b];
-            if (B.in[0] != A.in[0] || !plain3(b, 2) || B.segment != A.segment) continue;
+            if (B.in[0] != A.in[0] || !is_free(g, b) || !plain_conv(g, b, 3, 2, 1) || B.segment != A.segment) continue;
             if (!trans1_supported(x.h, x.w, x.c, A.cout, B.cout)) continue;
-            g.twin[a] = b;
-            g.absorbed[b] = 1;
+            Launch& L = emit(g, R_TWIN, a, {A.in[0]}, {A.out, B.out});
+            L.twin = b;
+            cover(g, L, b);
             break;
         }
     }
 }
 
-// Planar-layout pass: a fused Bottleneck whose output feeds only a fused transition1 (twin)
-// writes it chunk-planar ([N][16][H][W][16]) and trans1 reads it so: each 16-channel item of
-// trans1 is then contiguous in HBM instead of a quarter of every 128-B line (PMC: trans1 read
-// its 1.6 GB input 1.67 times).  Numerically a no-op.
+// Planar layout: a fused Bottleneck whose output feeds only a fused transition1 (its two convs
+// and nothing else) writes it chunk-planar ([N][16][H][W][16]) and trans1 reads it so: each
+// 16-channel item of trans1 is then contiguous in HBM instead of a quarter of every 128-B line
+// (PMC: trans1 read its 1.6 GB input 1.67 times).  Numerically a no-op.
 void planar_fuse(Graph& g) {
-    const int no = (int)g.ops.size();
-    g.planar.assign(no, 0);
-    for (int k = 0; k < no; k++) {
-        if (g.bneck[k] < 0 || g.bneck_lead[k]) continue;
-        const int t = g.ops[k].out;
-        if (t == g.output) continue;
-        int tw = -1, ok = 1;
-        for (int c = 0; c < no && ok; c++) {
-            const mvp_op_desc& op = g.ops[c];
-            for (int i = 0; i < op.n_in; i++) {
-                if (op.in[i] != t) continue;
-                if (i == 0 && g.twin[c] >= 0 && !g.absorbed[c] && tw < 0) tw = c;
-                else if (!(i == 0 && g.absorbed[c] && tw >= 0 && g.twin[tw] == c)) ok = 0;
-            }
-        }
-        if (ok && tw >= 0) {
-            g.planar[k] = 1;
-            g.planar[tw] = 1;
-        }
+    const UseDef ud = use_def(g, false);
+    for (Launch& T : g.launches) {
+        if (T.route != R_TWIN) continue;
+        const int t = T.reads[0];
+        Launch* B = launch_of(g, ud.producer[t]);
+        if (B && B->route == R_BNECK && !B->lead && ud.uses[t] == 2 && t != g.output) B->planar = T.planar = 1;
     }
 }
 
-// Sibling-fusion pass: in an HRModule fuse layer the branch-0 tensor (32 ch @ 64x48) is the
-// input of up to three 3x3/s2 convs (-> 64 ch for branch 1; -> 32 ch + ReLU starting the
-// chains to branches 2 and 3).  They run as ONE launch over cout-concatenated weights
-// (s2conv_multi): the 201 MB input is read once instead of once per conv.
-void sib_fuse(Graph& g, bool enable) {
+// Sibling fusion: in an HRModule fuse layer the branch-0 tensor (32 ch @ 64x48) is the input
+// of up to three 3x3/s2 convs (-> 64 ch for branch 1; -> 32 ch + ReLU starting the chains to
+// branches 2 and 3).  They run as ONE launch over cout-concatenated weights (s2conv_multi):
+// the 201 MB input is read once instead of once per conv.
+void sib_fuse(Graph& g) {
     const int no = (int)g.ops.size();
-    g.sib.assign(no, {});
-    g.sib_w.assign(no, nullptr);
-    g.t16_w.assign(no, nullptr);
-    g.tr_w.assign(no, nullptr);
-    g.sib_b.assign(no, nullptr);
-    if (!enable) return;
-    auto plain_s2 = [&](int k) {
-        const mvp_op_desc& op = g.ops[k];
-        return op.kind == MVP_OP_CONV && !g.absorbed[k] && !g.block_head[k] && g.cat_src[k] < 0 &&
-               g.pair_tail[k] < 0 && g.stem_head[k] < 0 && g.twin[k] < 0 && op.ks == 3 && op.stride == 2 &&
-               (op.n_in < 2 || op.in[1] < 0) && op.cout % 32 == 0 && g.tensors[op.out].dtype == MVP_DT_BF16_NHWC;
-    };
+    auto plain_s2 = [&](int k) { return is_free(g, k) && plain_conv(g, k, 3, 2, -1) && g.ops[k].cout % 32 == 0; };
     for (int a = 0; a < no; a++) {
         if (!plain_s2(a)) continue;
         const mvp_op_desc& A = g.ops[a];
@@ -431,150 +430,152 @@ void sib_fuse(Graph& g, bool enable) {
             tot += B.cout;
         }
         if (list.empty()) continue;
-        for (int b : list) g.absorbed[b] = 1;
-        g.sib[a] = list;
-    }
-}
-
-// Head-fusion pass: the last fuse layer's out0 (32 ch @ 64x48) feeds only the heatmap head
-// (1x1 32 -> 17, f32 NCHW); the head kernel forms out0 per pixel itself, so the 201 MB
-// tensor is never written or re-read (bit-identical: same sums, same bf16 rounding).
-void head_fuse(Graph& g, bool enable) {
-    const int no = (int)g.ops.size(), nt = (int)g.tensors.size();
-    g.head_src.assign(no, -1);
-    if (!enable) return;
-    std::vector<int> uses(nt, 0), producer(nt, -1);
-    for (int k = 0; k < no; k++) {
-        const mvp_op_desc& op = g.ops[k];
-        producer[op.out] = k;
-        for (int i = 0; i < op.n_in; i++)
-            if (op.in[i] >= 0) uses[op.in[i]]++;
-    }
-    for (int k = 0; k < no; k++) {
-        const mvp_op_desc& H = g.ops[k];
-        if (H.kind != MVP_OP_CONV || g.absorbed[k] || g.tensors[H.out].dtype != MVP_DT_F32_NCHW || H.ks != 1 ||
-            H.relu || (H.n_in > 1 && H.in[1] >= 0))
-            continue;
-        const int f = producer[H.in[0]];
-        if (f < 0 || g.absorbed[f] || g.ops[f].kind != MVP_OP_FUSE || uses[H.in[0]] != 1 || H.in[0] == g.output ||
-            g.ops[f].segment != H.segment)
-            continue;
-        if (!head_fuse_supported(H.cin, H.cout, g.ops[f].n_in)) continue;
-        g.absorbed[f] = 1;
-        g.head_src[k] = f;
-    }
-}
-
-// Device-side concatenated weights / summed biases of the cat-fused ops: allocated at graph
-// create time, filled from the blobs by cat_fill (create and mvp_graph_refresh_weights).
-void cat_alloc(Graph& g) {
-    for (int b = 0; b < (int)g.ops.size(); b++) {
-        const int a = g.cat_src[b];
-        if (a < 0) continue;
-        const mvp_op_desc& B = g.ops[b];
-        const int cp = conv_cout_pad(B.cout), cin = B.cin + g.ops[a].cin;
-        MVP_HIP(hipMalloc(&g.cat_w[b], (size_t)cp * cin * sizeof(uint16_t)));
-        MVP_HIP(hipMalloc(&g.cat_b[b], (size_t)cp * sizeof(float)));
-    }
-}
-
-void sib_alloc(Graph& g) {
-    for (int a = 0; a < (int)g.ops.size(); a++) {
-        if (g.sib[a].empty()) continue;
-        const int kk = 9 * g.ops[a].cin;
-        MVP_HIP(hipMalloc(&g.sib_w[a], (size_t)128 * kk * sizeof(uint16_t)));
-        MVP_HIP(hipMalloc(&g.sib_b[a], (size_t)128 * sizeof(float)));
-    }
-}
-
-void sib_fill(Graph& g) {
-    for (int a = 0; a < (int)g.ops.size(); a++) {
-        if (g.sib[a].empty()) continue;
-        const int kk = 9 * g.ops[a].cin;
-        MVP_HIP(hipMemset(g.sib_w[a], 0, (size_t)128 * kk * sizeof(uint16_t)));
-        MVP_HIP(hipMemset(g.sib_b[a], 0, (size_t)128 * sizeof(float)));
-        int row = 0;
-        std::vector<int> members{a};
-        members.insert(members.end(), g.sib[a].begin(), g.sib[a].end());
-        for (int m : members) {
-            const mvp_op_desc& op = g.ops[m];
-            MVP_HIP(hipMemcpy(g.sib_w[a] + (size_t)row * kk, g.wb + op.w_off, (size_t)op.cout * kk * sizeof(uint16_t),
-                              hipMemcpyDeviceToDevice));
-            MVP_HIP(hipMemcpy(g.sib_b[a] + row, g.fb + op.b_off, (size_t)op.cout * sizeof(float),
-                              hipMemcpyDeviceToDevice));
-            row += op.cout;
+        Launch& L = emit(g, R_SIBLINGS, a, {A.in[0]}, {A.out});
+        for (int b : list) {
+            L.writes.push_back(g.ops[b].out);
+            cover(g, L, b);
         }
     }
 }
 
-void cat_fill(Graph& g) {
-    for (int b = 0; b < (int)g.ops.size(); b++) {
-        const int a = g.cat_src[b];
-        if (a < 0) continue;
-        const mvp_op_desc& B = g.ops[b];
-        const mvp_op_desc& A = g.ops[a];
-        const int cp = conv_cout_pad(B.cout), cin = B.cin + A.cin;
-        MVP_HIP(hipMemcpy2D(g.cat_w[b], (size_t)cin * 2, g.wb + B.w_off, (size_t)B.cin * 2, (size_t)B.cin * 2, cp,
-                            hipMemcpyDeviceToDevice));
-        MVP_HIP(hipMemcpy2D(g.cat_w[b] + B.cin, (size_t)cin * 2, g.wb + A.w_off, (size_t)A.cin * 2,
-                            (size_t)A.cin * 2, cp, hipMemcpyDeviceToDevice));
-        std::vector<float> hb(cp), ha(cp);
-        MVP_HIP(hipMemcpy(hb.data(), g.fb + B.b_off, cp * sizeof(float), hipMemcpyDeviceToHost));
-        MVP_HIP(hipMemcpy(ha.data(), g.fb + A.b_off, cp * sizeof(float), hipMemcpyDeviceToHost));
-        for (int i = 0; i < cp; i++) hb[i] += ha[i];
-        MVP_HIP(hipMemcpy(g.cat_b[b], hb.data(), cp * sizeof(float), hipMemcpyHostToDevice));
+// Head fusion: the last fuse layer's out0 (32 ch @ 64x48) feeds only the heatmap head (1x1
+// 32 -> 17, f32 NCHW); the head kernel forms out0 per pixel itself, so the 201 MB tensor is
+// never written or re-read (bit-identical: same sums, same bf16 rounding).
+void head_fuse(Graph& g) {
+    const UseDef ud = use_def(g, false);
+    for (int k = 0; k < (int)g.ops.size(); k++) {
+        const mvp_op_desc& H = g.ops[k];
+        if (H.kind != MVP_OP_CONV || !is_free(g, k) || g.tensors[H.out].dtype != MVP_DT_F32_NCHW || H.ks != 1 ||
+            H.relu || has_res(H))
+            continue;
+        const int f = ud.producer[H.in[0]];
+        if (!is_free(g, f) || g.ops[f].kind != MVP_OP_FUSE || ud.uses[H.in[0]] != 1 || H.in[0] == g.output ||
+            g.ops[f].segment != H.segment)
+            continue;
+        const mvp_op_desc& F = g.ops[f];
+        if (!head_fuse_supported(H.cin, H.cout, F.n_in)) continue;
+        Launch& L = emit(g, R_HEAD_FUSE, k, std::vector<int>(F.in, F.in + F.n_in), {H.out});
+        L.fuse = f;
+        cover(g, L, f);
     }
 }
 
-// Weight images of the convs tconv16.hip serves (alloc at create, refilled with the blobs).
-long t16_elems(const Graph& g, int k) {
+int64_t op_macs(const Graph& g, int k) {
     const mvp_op_desc& op = g.ops[k];
-    if (op.kind != MVP_OP_CONV || g.absorbed[k] || g.cat_src[k] >= 0 || g.pair_tail[k] >= 0 || g.bneck[k] >= 0 ||
-        (op.stride == 1 && !op.relu) || g.tensors[op.out].dtype == MVP_DT_F32_NCHW || !g.sib[k].empty() ||
-        g.twin[k] >= 0 || g.stem_head[k] >= 0)
+    if (op.kind != MVP_OP_CONV && op.kind != MVP_OP_STEM) return 0;
+    const mvp_tensor_desc& o = g.tensors[op.out];
+    const int cin = op.kind == MVP_OP_STEM ? 3 : op.cin;
+    return (int64_t)o.h * o.w * op.cout * cin * op.ks * op.ks;
+}
+
+// Every op no pass claimed launches on its own; then the list goes into op order (= launch
+// order) and each segment gets its range of it.
+void finish_launches(Graph& g) {
+    const int no = (int)g.ops.size();
+    for (int k = 0; k < no; k++) {
+        const mvp_op_desc& op = g.ops[k];
+        if (!is_free(g, k)) continue;
+        if (op.kind == MVP_OP_CONV) emit_conv(g, k);
+        else if (op.kind == MVP_OP_STEM) emit(g, R_STEM, k, {op.in[0]}, {op.out});
+        else emit(g, R_FUSE_SUM, k, std::vector<int>(op.in, op.in + op.n_in), {op.out});
+    }
+    std::sort(g.launches.begin(), g.launches.end(), [](const Launch& a, const Launch& b) { return a.op < b.op; });
+    std::vector<int> covered(no, 0);
+    for (Segment& sg : g.segs) sg.first_launch = sg.end_launch = 0;
+    for (int l = 0; l < (int)g.launches.size(); l++) {
+        Launch& L = g.launches[l];
+        for (int k : L.covers) {
+            g.owner[k] = l;
+            covered[k]++;
+            L.macs += op_macs(g, k);
+        }
+        Segment& sg = g.segs[g.ops[L.op].segment];
+        if (sg.end_launch == 0) sg.first_launch = l;
+        sg.end_launch = l + 1;
+    }
+    for (int k = 0; k < no; k++) MVP_REQUIRE(covered[k] == 1, "graph: op %d covered by %d launches", k, covered[k]);
+}
+
+// ---- derived weights ---------------------------------------------------------------------
+// Device-side weights a launch owns: allocated at graph create time, filled from the blobs by
+// fill_weights (create and mvp_graph_refresh_weights).
+
+long t16_elems(const Graph& g, const Launch& L) {
+    const mvp_op_desc& op = g.ops[L.op];
+    if (L.route != R_CONV || L.cat_src >= 0 || (op.stride == 1 && !op.relu) ||
+        g.tensors[op.out].dtype == MVP_DT_F32_NCHW)
         return 0;
     const mvp_tensor_desc& x = g.tensors[op.in[0]];
     return tconv16_image_elems(op.cin, op.cout, x.h, x.w, op.ks, op.stride);
 }
 
-void t16_alloc(Graph& g) {
-    for (int k = 0; k < (int)g.ops.size(); k++) {
-        const long n = t16_elems(g, k);
-        if (n > 0) MVP_HIP(hipMalloc(&g.t16_w[k], (size_t)n * sizeof(uint16_t)));
-        if (g.twin[k] >= 0 && !g.absorbed[k]) MVP_HIP(hipMalloc(&g.tr_w[k], (size_t)kTrans1ImageElems * sizeof(uint16_t)));
+void alloc_weights(Graph& g) {
+    for (Launch& L : g.launches) {
+        const mvp_op_desc& op = g.ops[L.op];
+        if (L.cat_src >= 0) {
+            const int cp = conv_cout_pad(op.cout), cin = op.cin + g.ops[L.cat_src].cin;
+            MVP_HIP(hipMalloc(&L.w, (size_t)cp * cin * sizeof(uint16_t)));
+            MVP_HIP(hipMalloc(&L.b, (size_t)cp * sizeof(float)));
+        } else if (L.route == R_SIBLINGS) {
+            MVP_HIP(hipMalloc(&L.w, (size_t)128 * 9 * op.cin * sizeof(uint16_t)));
+            MVP_HIP(hipMalloc(&L.b, (size_t)128 * sizeof(float)));
+        } else if (L.route == R_TWIN) {
+            MVP_HIP(hipMalloc(&L.w_img, (size_t)kTrans1ImageElems * sizeof(uint16_t)));
+        } else if (const long n = t16_elems(g, L)) {
+            MVP_HIP(hipMalloc(&L.w_img, (size_t)n * sizeof(uint16_t)));
+        }
     }
 }
 
-void t16_fill(Graph& g) {
-    for (int k = 0; k < (int)g.ops.size(); k++) {
-        if (g.t16_w[k]) tconv16_pack_weights(g.wb + g.ops[k].w_off, g.t16_w[k], g.ops[k].cin, g.ops[k].cout, nullptr);
-        if (g.tr_w[k]) trans1_pack_weights(g.wb, g.ops[k].w_off, g.ops[g.twin[k]].w_off, g.tr_w[k], nullptr);
+void fill_weights(Graph& g) {
+    for (Launch& L : g.launches) {
+        const mvp_op_desc& op = g.ops[L.op];
+        if (L.cat_src >= 0) {  // [W | W_src], bias + bias_src
+            const mvp_op_desc& A = g.ops[L.cat_src];
+            const int cp = conv_cout_pad(op.cout), cin = op.cin + A.cin;
+            MVP_HIP(hipMemcpy2D(L.w, (size_t)cin * 2, g.wb + op.w_off, (size_t)op.cin * 2, (size_t)op.cin * 2, cp,
+                                hipMemcpyDeviceToDevice));
+            MVP_HIP(hipMemcpy2D(L.w + op.cin, (size_t)cin * 2, g.wb + A.w_off, (size_t)A.cin * 2, (size_t)A.cin * 2,
+                                cp, hipMemcpyDeviceToDevice));
+            std::vector<float> hb(cp), ha(cp);
+            MVP_HIP(hipMemcpy(hb.data(), g.fb + op.b_off, cp * sizeof(float), hipMemcpyDeviceToHost));
+            MVP_HIP(hipMemcpy(ha.data(), g.fb + A.b_off, cp * sizeof(float), hipMemcpyDeviceToHost));
+            for (int i = 0; i < cp; i++) hb[i] += ha[i];
+            MVP_HIP(hipMemcpy(L.b, hb.data(), cp * sizeof(float), hipMemcpyHostToDevice));
+        } else if (L.route == R_SIBLINGS) {  // the members' rows one after another, zero rows after them
+            const int kk = 9 * op.cin;
+            MVP_HIP(hipMemset(L.w, 0, (size_t)128 * kk * sizeof(uint16_t)));
+            MVP_HIP(hipMemset(L.b, 0, (size_t)128 * sizeof(float)));
+            int row = 0;
+            for (int m : L.covers) {
+                const mvp_op_desc& o = g.ops[m];
+                MVP_HIP(hipMemcpy(L.w + (size_t)row * kk, g.wb + o.w_off, (size_t)o.cout * kk * sizeof(uint16_t),
+                                  hipMemcpyDeviceToDevice));
+                MVP_HIP(hipMemcpy(L.b + row, g.fb + o.b_off, (size_t)o.cout * sizeof(float), hipMemcpyDeviceToDevice));
+                row += o.cout;
+            }
+        } else if (L.route == R_TWIN) {
+            trans1_pack_weights(g.wb, op.w_off, g.ops[L.twin].w_off, L.w_img, nullptr);
+        } else if (L.w_img) {
+            tconv16_pack_weights(g.wb + op.w_off, L.w_img, op.cin, op.cout, nullptr);
+        }
     }
     MVP_HIP(hipDeviceSynchronize());
 }
 
-void cat_free(Graph& g) {
-    for (uint16_t* p : g.t16_w)
-        if (p) (void)hipFree(p);
-    for (uint16_t* p : g.tr_w)
-        if (p) (void)hipFree(p);
-    g.t16_w.clear();
-    g.tr_w.clear();
-    for (uint16_t* p : g.cat_w)
-        if (p) (void)hipFree(p);
-    for (float* p : g.cat_b)
-        if (p) (void)hipFree(p);
-    for (uint16_t* p : g.sib_w)
-        if (p) (void)hipFree(p);
-    for (float* p : g.sib_b)
-        if (p) (void)hipFree(p);
-    g.cat_w.clear();
-    g.cat_b.clear();
-    g.sib_w.clear();
-    g.sib_b.clear();
+void free_weights(Graph& g) {
+    for (Launch& L : g.launches) {
+        if (L.w) (void)hipFree(L.w);
+        if (L.b) (void)hipFree(L.b);
+        if (L.w_img) (void)hipFree(L.w_img);
+        L.w = L.w_img = nullptr;
+        L.b = nullptr;
+    }
 }
 
-// Greedy first-fit placement of tensors in one arena by lifetime [def, last use].
+// ---- arena ----------------------------------------------------------------------------------
+// Greedy first-fit placement of tensors in one arena by lifetime [def, last use], both taken
+// from the launches' read / write lists at their launching op's index.
 // A tensor produced and consumed only inside one micro-batched segment is
 // "local": it is sized for one micro-batch and re-used by every micro-batch.
 // Every other tensor a micro-batched segment touches is sliced per micro-batch,
@@ -582,69 +583,23 @@ void cat_free(Graph& g) {
 // the segment's ops).
 void plan(Graph& g) {
     const int nt = (int)g.tensors.size();
-    const int no = (int)g.ops.size();
     std::vector<int> first(nt, -1), last(nt, -1);
     std::vector<int> seg_of_def(nt, -1);
     std::vector<int> multi_seg(nt, 0);  // used by more than one segment
     std::vector<int> use_seg(nt, -1);
-    for (int k = 0; k < no; k++) {
-        if (g.absorbed[k]) continue;  // its output lives only in the fused kernel's LDS
-        const mvp_op_desc& op = g.ops[k];
-        first[op.out] = k;
-        if (last[op.out] < k) last[op.out] = k;
-        seg_of_def[op.out] = op.segment;
+    for (const Launch& L : g.launches) {
+        const int k = L.op, seg = g.ops[k].segment;
         auto touch = [&](int t) {
-            if (use_seg[t] < 0) use_seg[t] = op.segment;
-            else if (use_seg[t] != op.segment) multi_seg[t] = 1;
+            last[t] = std::max(last[t], k);
+            if (use_seg[t] < 0) use_seg[t] = seg;
+            else if (use_seg[t] != seg) multi_seg[t] = 1;
         };
-        touch(op.out);
-        for (int i = 0; i < op.n_in; i++) {
-            if (op.in[i] < 0 || (g.block_head[k] && i == 0)) continue;  // fused: conv1's output is LDS-only
-            if (g.stem_head[k] >= 0 && i == 0) continue;                 // fused stem: LDS-only
-            if (g.head_src[k] >= 0 && i == 0) continue;                  // fused head: never materialised
-            if (g.cat_src[k] >= 0 && i == 1) continue;                  // cat-fused: never materialised
-            if (g.bneck[k] >= 0 && i == 0) continue;                     // fused Bottleneck: LDS-only
-            last[op.in[i]] = std::max(last[op.in[i]], k);
-            touch(op.in[i]);
+        for (int t : L.writes) {
+            first[t] = k;
+            seg_of_def[t] = seg;
+            touch(t);
         }
-        if (g.cat_src[k] >= 0) {  // the absorbed op's input is read here
-            const int x = g.ops[g.cat_src[k]].in[0];
-            last[x] = std::max(last[x], k);
-            touch(x);
-        }
-        if (g.twin[k] >= 0) {  // the absorbed sibling's output is written here
-            const int y2 = g.ops[g.twin[k]].out;
-            first[y2] = k;
-            if (last[y2] < k) last[y2] = k;
-            seg_of_def[y2] = op.segment;
-            touch(y2);
-        }
-        for (int b : g.sib[k]) {  // the absorbed siblings' outputs are written here
-            const int y2 = g.ops[b].out;
-            first[y2] = k;
-            if (last[y2] < k) last[y2] = k;
-            seg_of_def[y2] = op.segment;
-            touch(y2);
-        }
-        if (g.stem_head[k] >= 0) {  // the absorbed stem's input is read here
-            const int x = g.ops[g.stem_head[k]].in[0];
-            last[x] = std::max(last[x], k);
-            touch(x);
-        }
-        if (g.head_src[k] >= 0) {  // the absorbed fuse's inputs are read here
-            const mvp_op_desc& f = g.ops[g.head_src[k]];
-            for (int i = 0; i < f.n_in; i++) {
-                last[f.in[i]] = std::max(last[f.in[i]], k);
-                touch(f.in[i]);
-            }
-        }
-        if (g.pair_tail[k] >= 0) {  // the absorbed successor's output is written here
-            const int y2 = g.ops[g.pair_tail[k]].out;
-            first[y2] = k;
-            if (last[y2] < k) last[y2] = k;
-            seg_of_def[y2] = op.segment;
-            touch(y2);
-        }
+        for (int t : L.reads) touch(t);
     }
     g.local_seg.assign(nt, -1);
     for (int t = 0; t < nt; t++) {
@@ -652,28 +607,16 @@ void plan(Graph& g) {
         const int sg = seg_of_def[t];
         if (!multi_seg[t] && g.segs[sg].micro_batch > 0 && g.segs[sg].micro_batch < g.max_batch) g.local_seg[t] = sg;
     }
-    for (int k = 0; k < no; k++) {
-        if (g.absorbed[k]) continue;
-        const mvp_op_desc& op = g.ops[k];
-        const Segment& sg = g.segs[op.segment];
+    for (const Launch& L : g.launches) {
+        const Segment& sg = g.segs[g.ops[L.op].segment];
         if (sg.micro_batch <= 0 || sg.micro_batch >= g.max_batch) continue;
         auto widen = [&](int t) {
-            if (t < 0 || g.local_seg[t] >= 0) return;
+            if (g.local_seg[t] >= 0) return;
             first[t] = std::min(first[t] < 0 ? sg.first_op : first[t], sg.first_op);
             last[t] = std::max(last[t], sg.last_op);
         };
-        widen(op.out);
-        for (int i = 0; i < op.n_in; i++)
-            if (!(g.block_head[k] && i == 0) && !(g.cat_src[k] >= 0 && i == 1) && !(g.stem_head[k] >= 0 && i == 0) &&
-                !(g.head_src[k] >= 0 && i == 0) && !(g.bneck[k] >= 0 && i == 0))
-                widen(op.in[i]);
-        if (g.head_src[k] >= 0)
-            for (int i = 0; i < g.ops[g.head_src[k]].n_in; i++) widen(g.ops[g.head_src[k]].in[i]);
-        if (g.stem_head[k] >= 0) widen(g.ops[g.stem_head[k]].in[0]);
-        if (g.twin[k] >= 0) widen(g.ops[g.twin[k]].out);
-        for (int b : g.sib[k]) widen(g.ops[b].out);
-        if (g.cat_src[k] >= 0) widen(g.ops[g.cat_src[k]].in[0]);
-        if (g.pair_tail[k] >= 0) widen(g.ops[g.pair_tail[k]].out);
+        for (int t : L.writes) widen(t);
+        for (int t : L.reads) widen(t);
     }
     std::vector<int> order;
     for (int t = 0; t < nt; t++)
@@ -708,10 +651,21 @@ void plan(Graph& g) {
     g.arena_bytes = top;
 }
 
+// Micro-batches of one forward of `batch` crops, segment by segment: fn(segment, first crop, crops).
+template <class F>
+void for_each_micro_batch(const Graph& g, int batch, F fn) {
+    for (const Segment& sg : g.segs) {
+        const int mb = (sg.micro_batch > 0 && sg.micro_batch < batch) ? sg.micro_batch : batch;
+        for (int64_t b0 = 0; b0 < batch && sg.first_launch < sg.end_launch; b0 += mb)
+            fn(sg, b0, (int)std::min<int64_t>(mb, batch - b0));
+    }
+}
+
 }  // namespace
 }  // namespace mvp
 
 using mvp::Graph;
+using mvp::Launch;
 
 extern "C" int mvp_graph_create(const mvp_tensor_desc* tensors, int n_tensors, const mvp_op_desc* ops, int n_ops,
                                 const int* seg_micro_batch, int n_segments, int input_tensor, int output_tensor,
@@ -741,25 +695,24 @@ extern "C" int mvp_graph_create(const mvp_tensor_desc* tensors, int n_tensors, c
             g->segs[i].micro_batch = seg_micro_batch[i];
         }
         mvp::validate(*g, w_elems, f_elems);
-        const char* nf = getenv("MVPOSE_NO_FUSE");  // diagnostics: run every conv on its own
-        mvp::fuse(*g, !(nf && nf[0] == '1'));
-        const char* nc = getenv("MVPOSE_NO_CATFUSE");  // diagnostics: keep the downsample conv separate
-        mvp::cat_fuse(*g, !(nc && nc[0] == '1') && !(nf && nf[0] == '1'));
-        const char* np = getenv("MVPOSE_NO_PAIRFUSE");  // diagnostics: keep conv3 / next conv1 apart
-        const bool pair_on = !(np && np[0] == '1') && !(nf && nf[0] == '1');
-        mvp::bneck_fuse(*g, !(nf && nf[0] == '1'), pair_on && mvp::conv1x1_pair_supported(64, 256, 64));
-        mvp::pair_fuse(*g, pair_on);
-        mvp::stem_fuse(*g, !(nf && nf[0] == '1'));
-        mvp::twin_fuse(*g, !(nf && nf[0] == '1'));
-        mvp::planar_fuse(*g);
-        mvp::sib_fuse(*g, !(nf && nf[0] == '1'));
-        mvp::head_fuse(*g, !(nf && nf[0] == '1'));
-        mvp::cat_alloc(*g);
-        mvp::sib_alloc(*g);
-        mvp::cat_fill(*g);
-        mvp::sib_fill(*g);
-        mvp::t16_alloc(*g);
-        mvp::t16_fill(*g);
+        g->owner.assign(n_ops, -1);
+        g->launches.reserve(n_ops);  // the passes hold Launch references across emit()
+        // diagnostics: MVPOSE_NO_FUSE=1 runs every op on its own, MVPOSE_NO_CATFUSE=1 keeps the
+        // downsample conv separate; the kernels' *_supported() read the other switches
+        if (!mvp::env_set("MVPOSE_NO_FUSE")) {
+            mvp::fuse(*g);
+            if (!mvp::env_set("MVPOSE_NO_CATFUSE")) mvp::cat_fuse(*g);
+            mvp::bneck_fuse(*g, mvp::conv1x1_pair_supported(64, 256, 64));
+            mvp::pair_fuse(*g);
+            mvp::stem_fuse(*g);
+            mvp::twin_fuse(*g);
+            mvp::planar_fuse(*g);
+            mvp::sib_fuse(*g);
+            mvp::head_fuse(*g);
+        }
+        mvp::finish_launches(*g);
+        mvp::alloc_weights(*g);
+        mvp::fill_weights(*g);
         mvp::plan(*g);
         if (g->arena_bytes > 0) {
             hipError_t e = hipMalloc(&g->arena, g->arena_bytes);
@@ -768,7 +721,7 @@ extern "C" int mvp_graph_create(const mvp_tensor_desc* tensors, int n_tensors, c
                           hipGetErrorString(e));
         }
     } catch (...) {
-        mvp::cat_free(*g);
+        mvp::free_weights(*g);
         delete g;
         throw;
     }
@@ -794,226 +747,135 @@ extern "C" int mvp_graph_forward(void* handle, const void* input_dev, int batch,
                                       : g->arena + g->offset[t];
         return base + slice * mvp::tensor_bytes(d, 1);
     };
-    auto run_op = [&](int k, int nb) {
-        const mvp_op_desc& op = g->ops[k];
+    auto bf16 = [&](int t) { return (uint16_t*)ptr(t); };
+    auto run = [&](const Launch& L, int nb) {
+        const mvp_op_desc& op = g->ops[L.op];
         const mvp_tensor_desc& o = g->tensors[op.out];
-        if (g->absorbed[k]) return;
-        if (g->block_head[k]) {
-            const mvp_op_desc& c1 = g->ops[k - 1];
+        const mvp_tensor_desc& x = g->tensors[L.reads[0]];
+        switch (L.route) {
+        case mvp::R_BLOCK: {
+            const mvp_op_desc& c1 = g->ops[L.op - 1];
             auto launch = c1.cin == 32 ? mvp::launch_basic_block_c32 : mvp::launch_tblock64;
-            launch((const uint16_t*)ptr(op.in[1]), g->wb + c1.w_off, g->fb + c1.b_off, g->wb + op.w_off,
-                   g->fb + op.b_off, (uint16_t*)ptr(op.out), nb, o.h, o.w, s);
-            return;
+            launch(bf16(op.in[1]), g->wb + c1.w_off, g->fb + c1.b_off, g->wb + op.w_off, g->fb + op.b_off,
+                   bf16(op.out), nb, o.h, o.w, s);
+            break;
         }
-        if (g->twin[k] >= 0) {  // transition1: this 3x3/s1 conv and its 3x3/s2 sibling, one pass
-            const mvp_op_desc& b = g->ops[g->twin[k]];
-            mvp::launch_trans1((const uint16_t*)ptr(op.in[0]), g->wb, op.w_off, g->fb + op.b_off, b.w_off,
-                               g->fb + b.b_off, (uint16_t*)ptr(op.out), (uint16_t*)ptr(b.out), nb, s, g->tr_w[k],
-                               g->planar[k]);
-            return;
+        case mvp::R_TWIN: {  // transition1: this 3x3/s1 conv and its 3x3/s2 sibling, one pass
+            const mvp_op_desc& b = g->ops[L.twin];
+            mvp::launch_trans1(bf16(op.in[0]), g->wb, op.w_off, g->fb + op.b_off, b.w_off, g->fb + b.b_off,
+                               bf16(op.out), bf16(b.out), nb, s, L.w_img, L.planar);
+            break;
         }
-        if (!g->sib[k].empty()) {  // this 3x3/s2 conv and its siblings on the same input
-            const mvp_tensor_desc& x = g->tensors[op.in[0]];
+        case mvp::R_SIBLINGS: {  // this 3x3/s2 conv and its siblings on the same input
             mvp::S2Multi m;
-            m.x = (const uint16_t*)ptr(op.in[0]);
-            m.w = g->sib_w[k];
-            m.bias = g->sib_b[k];
-            m.N = nb;
-            m.H = x.h;
-            m.W = x.w;
-            m.Cin = op.cin;
-            std::vector<int> members{k};
-            members.insert(members.end(), g->sib[k].begin(), g->sib[k].end());
-            m.n_out = (int)members.size();
+            m.x = bf16(op.in[0]), m.w = L.w, m.bias = L.b;
+            m.N = nb, m.H = x.h, m.W = x.w, m.Cin = op.cin;
+            m.n_out = (int)L.covers.size();
             for (int i = 0; i < m.n_out; i++) {
-                const mvp_op_desc& o2 = g->ops[members[i]];
-                m.y[i] = (uint16_t*)ptr(o2.out);
-                m.cout[i] = o2.cout;
-                m.relu[i] = o2.relu;
+                const mvp_op_desc& o2 = g->ops[L.covers[i]];
+                m.y[i] = bf16(o2.out), m.cout[i] = o2.cout, m.relu[i] = o2.relu;
             }
             mvp::launch_s2conv_multi(m, s);
-            return;
+            break;
         }
-        if (g->head_src[k] >= 0) {  // the last fuse layer's out0, formed per pixel by the head
-            const mvp_op_desc& f = g->ops[g->head_src[k]];
+        case mvp::R_HEAD_FUSE: {  // the last fuse layer's out0, formed per pixel by the head
+            const mvp_op_desc& f = g->ops[L.fuse];
             const mvp_tensor_desc& fo = g->tensors[f.out];
             const uint16_t* ins[4];
-            for (int i = 0; i < f.n_in; i++) ins[i] = (const uint16_t*)ptr(f.in[i]);
+            for (int i = 0; i < f.n_in; i++) ins[i] = bf16(f.in[i]);
             mvp::launch_head_fuse(ins, f.up, f.n_in, f.relu, g->wb + op.w_off, g->fb + op.b_off, (float*)ptr(op.out),
                                   nb, fo.h, fo.w, s);
-            return;
+            break;
         }
-        if (g->bneck[k] >= 0) {  // the whole Bottleneck: conv1 + conv2 (absorbed) + this conv3
-            const mvp_op_desc& a = g->ops[g->bneck[k]];
-            const mvp_op_desc& c2 = g->ops[g->bneck_mid[k]];
-            const bool lead = g->bneck_lead[k];
-            const mvp_tensor_desc& x = g->tensors[a.in[0]];
+        case mvp::R_BNECK: {  // the whole Bottleneck: conv1 + conv2 + this conv3
+            const mvp_op_desc& a = g->ops[L.conv1];
+            const mvp_op_desc& c2 = g->ops[L.conv2];
             mvp::BneckLaunch bl;
-            bl.x = (const uint16_t*)ptr(a.in[0]);
-            bl.w1 = g->wb + a.w_off;
-            bl.b1 = g->fb + a.b_off;
-            bl.w2 = g->wb + c2.w_off;
-            bl.b2 = g->fb + c2.b_off;
-            bl.w3 = lead ? g->cat_w[k] : g->wb + op.w_off;
-            bl.b3 = lead ? g->cat_b[k] : g->fb + op.b_off;
-            bl.y = (uint16_t*)ptr(op.out);
-            bl.N = nb;
-            bl.H = x.h;
-            bl.W = x.w;
-            bl.perm = g->bneck_perm[k];
-            bl.lead = lead;
-            bl.planar = g->planar[k];
+            bl.x = bf16(a.in[0]);
+            bl.w1 = g->wb + a.w_off, bl.b1 = g->fb + a.b_off;
+            bl.w2 = g->wb + c2.w_off, bl.b2 = g->fb + c2.b_off;
+            bl.w3 = L.lead ? L.w : g->wb + op.w_off, bl.b3 = L.lead ? L.b : g->fb + op.b_off;
+            bl.y = bf16(op.out);
+            bl.N = nb, bl.H = x.h, bl.W = x.w;
+            bl.perm = L.perm, bl.lead = L.lead, bl.planar = L.planar;
             mvp::launch_bneck(bl, s);
-            return;
+            break;
         }
-        if (g->stem_head[k] >= 0) {  // stem conv1 + this conv2 in one launch
-            const mvp_op_desc& st = g->ops[g->stem_head[k]];
-            const mvp_tensor_desc& x = g->tensors[st.in[0]];
-            mvp::launch_stem2((const uint16_t*)ptr(st.in[0]), g->fb + st.w_off, g->fb + st.b_off, g->wb + op.w_off,
-                              g->fb + op.b_off, (uint16_t*)ptr(op.out), nb, x.h, x.w, s);
-            return;
+        case mvp::R_STEM2: {  // stem conv1 + this conv2 in one launch
+            const mvp_op_desc& st = g->ops[L.stem];
+            mvp::launch_stem2(bf16(st.in[0]), g->fb + st.w_off, g->fb + st.b_off, g->wb + op.w_off, g->fb + op.b_off,
+                              bf16(op.out), nb, x.h, x.w, s);
+            break;
         }
-        if (op.kind == MVP_OP_STEM) {
-            const mvp_tensor_desc& x = g->tensors[op.in[0]];
-            mvp::launch_stem((const uint16_t*)ptr(op.in[0]), g->fb + op.w_off, g->fb + op.b_off,
-                             (uint16_t*)ptr(op.out), nb, x.h, x.w, s);
-        } else if (op.kind == MVP_OP_CONV) {
-            const mvp_tensor_desc& x = g->tensors[op.in[0]];
+        case mvp::R_STEM:
+            mvp::launch_stem(bf16(op.in[0]), g->fb + op.w_off, g->fb + op.b_off, bf16(op.out), nb, x.h, x.w, s);
+            break;
+        case mvp::R_CONV:
+        case mvp::R_PAIR: {
             mvp::ConvLaunch c{};
-            c.x = (const uint16_t*)ptr(op.in[0]);
-            c.w = g->wb + op.w_off;
-            c.bias = g->fb + op.b_off;
-            c.res = (op.n_in > 1 && op.in[1] >= 0) ? (const uint16_t*)ptr(op.in[1]) : nullptr;
+            c.x = bf16(op.in[0]);
+            c.w = g->wb + op.w_off, c.bias = g->fb + op.b_off;
+            c.res = mvp::has_res(op) ? bf16(op.in[1]) : nullptr;
             c.out_f32_nchw = o.dtype == MVP_DT_F32_NCHW;
-            c.y = c.out_f32_nchw ? nullptr : (uint16_t*)ptr(op.out);
+            c.y = c.out_f32_nchw ? nullptr : bf16(op.out);
             c.yf = c.out_f32_nchw ? (float*)ptr(op.out) : nullptr;
-            c.N = nb;
-            c.H = x.h;
-            c.W = x.w;
-            c.Cin = op.cin;
-            c.Cout = op.cout;
-            c.ks = op.ks;
-            c.stride = op.stride;
-            c.relu = op.relu;
-            c.w_img = g->t16_w[k];
-            if (g->cat_src[k] >= 0) {  // cat-fused: [in[0], absorbed op's input] x [W | W_absorbed]
-                const mvp_op_desc& a = g->ops[g->cat_src[k]];
-                c.x2 = (const uint16_t*)ptr(a.in[0]);
-                c.c1 = op.cin;
-                c.Cin = op.cin + a.cin;
-                c.w = g->cat_w[k];
-                c.bias = g->cat_b[k];
-                c.res = nullptr;
+            c.N = nb, c.H = x.h, c.W = x.w;
+            c.Cin = op.cin, c.Cout = op.cout, c.ks = op.ks, c.stride = op.stride, c.relu = op.relu;
+            c.w_img = L.w_img;
+            if (L.cat_src >= 0) {  // cat-fused: [in[0], absorbed op's input] x [W | W_absorbed]
+                const mvp_op_desc& a = g->ops[L.cat_src];
+                c.x2 = bf16(a.in[0]), c.c1 = op.cin, c.Cin = op.cin + a.cin;
+                c.w = L.w, c.bias = L.b, c.res = nullptr;
             }
-            if (g->pair_tail[k] >= 0) {  // Bottleneck join: this conv + the next block's conv1
-                const mvp_op_desc& b = g->ops[g->pair_tail[k]];
-                mvp::PairLaunch pl;
-                pl.x = c.x;
-                pl.x2 = c.x2;
-                pl.c1 = c.x2 ? c.c1 : c.Cin;
-                pl.c2 = c.x2 ? c.Cin - c.c1 : 0;
-                pl.w1 = c.w;
-                pl.b1 = c.bias;
-                pl.res = c.res;
-                pl.y = c.y;
-                pl.w2 = g->wb + b.w_off;
-                pl.b2 = g->fb + b.b_off;
-                pl.y2 = (uint16_t*)ptr(b.out);
-                pl.n_pix = (long)nb * x.h * x.w;
-                mvp::launch_conv1x1_pair(pl, s);
-                return;
+            if (L.route == mvp::R_CONV) {
+                mvp::launch_conv(c, s);
+                break;
             }
-            mvp::launch_conv(c, s);
-        } else {
+            const mvp_op_desc& b = g->ops[L.tail];  // Bottleneck join: this conv + the next block's conv1
+            mvp::PairLaunch pl;
+            pl.x = c.x, pl.x2 = c.x2;
+            pl.c1 = c.x2 ? c.c1 : c.Cin, pl.c2 = c.x2 ? c.Cin - c.c1 : 0;
+            pl.w1 = c.w, pl.b1 = c.bias, pl.res = c.res, pl.y = c.y;
+            pl.w2 = g->wb + b.w_off, pl.b2 = g->fb + b.b_off, pl.y2 = bf16(b.out);
+            pl.n_pix = (long)nb * x.h * x.w;
+            mvp::launch_conv1x1_pair(pl, s);
+            break;
+        }
+        case mvp::R_FUSE_SUM: {
             const uint16_t* ins[4];
-            for (int i = 0; i < op.n_in; i++) ins[i] = (const uint16_t*)ptr(op.in[i]);
-            mvp::launch_fuse_sum(ins, op.up, op.n_in, (uint16_t*)ptr(op.out), nb, o.h, o.w, o.c, op.relu, s);
+            for (int i = 0; i < op.n_in; i++) ins[i] = bf16(op.in[i]);
+            mvp::launch_fuse_sum(ins, op.up, op.n_in, bf16(op.out), nb, o.h, o.w, o.c, op.relu, s);
+            break;
+        }
         }
     };
-    for (const mvp::Segment& sg : g->segs) {
-        if (sg.last_op < sg.first_op) continue;
-        const int mb = (sg.micro_batch > 0 && sg.micro_batch < batch) ? sg.micro_batch : batch;
-        for (int64_t b0 = 0; b0 < batch; b0 += mb) {
-            slice = b0;
-            const int nb = (int)std::min<int64_t>(mb, batch - b0);
-            for (int k = sg.first_op; k <= sg.last_op; k++) run_op(k, nb);
-        }
-        slice = 0;
-    }
+    mvp::for_each_micro_batch(*g, batch, [&](const mvp::Segment& sg, int64_t b0, int nb) {
+        slice = b0;
+        for (int l = sg.first_launch; l < sg.end_launch; l++) run(g->launches[l], nb);
+    });
     MVP_ABI_END
 }
 
 // Launch plan of one forward (diagnostics for tools/fwd_breakdown.py: pairs the kernel trace with
 // the graph's MACs so each kernel family gets its FLOP and MFMA fraction).  One record per kernel
 // launch, in launch order: {launching op, route, crops in the launch, MACs of every op it covers}.
-// route: 1 fused BasicBlock, 2 transition twin, 3 s2 siblings, 4 head + fuse, 5 Bottleneck,
-// 6 stem pair, 7 stem, 8 conv, 9 1x1 pair, 10 fuse sum.
-namespace {
-int64_t op_macs(const Graph& g, int k) {
-    const mvp_op_desc& op = g.ops[k];
-    if (op.kind != MVP_OP_CONV && op.kind != MVP_OP_STEM) return 0;
-    const mvp_tensor_desc& o = g.tensors[op.out];
-    const int cin = op.kind == MVP_OP_STEM ? 3 : op.cin;
-    return (int64_t)o.h * o.w * op.cout * cin * op.ks * op.ks;
-}
-}  // namespace
-
 extern "C" int mvp_graph_plan(void* handle, int batch, int64_t* rec_out, int max_records, int* n_records,
                               int64_t* covered_macs_out) {
     MVP_ABI_BEGIN
     Graph* g = static_cast<Graph*>(handle);
     MVP_REQUIRE(g && rec_out && n_records, "mvp_graph_plan: NULL pointer");
     MVP_REQUIRE(batch > 0 && batch <= g->max_batch, "mvp_graph_plan: batch %d", batch);
-    const int no = (int)g->ops.size();
-    std::vector<int> seen(no, 0);
     int n = 0;
     int64_t total = 0;
-    for (const mvp::Segment& sg : g->segs) {
-        if (sg.last_op < sg.first_op) continue;
-        const int mb = (sg.micro_batch > 0 && sg.micro_batch < batch) ? sg.micro_batch : batch;
-        for (int64_t b0 = 0; b0 < batch; b0 += mb) {
-            const int nb = (int)std::min<int64_t>(mb, batch - b0);
-            for (int k = sg.first_op; k <= sg.last_op; k++) {
-                if (g->absorbed[k]) continue;
-                const mvp_op_desc& op = g->ops[k];
-                std::vector<int> cov{k};
-                int route;
-                if (g->block_head[k]) { route = 1; cov.push_back(k - 1); }
-                else if (g->twin[k] >= 0) { route = 2; cov.push_back(g->twin[k]); }
-                else if (!g->sib[k].empty()) { route = 3; cov.insert(cov.end(), g->sib[k].begin(), g->sib[k].end()); }
-                else if (g->head_src[k] >= 0) { route = 4; cov.push_back(g->head_src[k]); }
-                else if (g->bneck[k] >= 0) {
-                    route = 5;
-                    cov.push_back(g->bneck[k]);
-                    cov.push_back(g->bneck_mid[k]);
-                    if (g->cat_src[k] >= 0) cov.push_back(g->cat_src[k]);
-                }
-                else if (g->stem_head[k] >= 0) { route = 6; cov.push_back(g->stem_head[k]); }
-                else if (op.kind == MVP_OP_STEM) route = 7;
-                else if (op.kind == MVP_OP_CONV) {
-                    route = g->pair_tail[k] >= 0 ? 9 : 8;
-                    if (g->cat_src[k] >= 0) cov.push_back(g->cat_src[k]);
-                    if (g->pair_tail[k] >= 0) cov.push_back(g->pair_tail[k]);
-                } else route = 10;
-                int64_t macs = 0;
-                for (int c : cov) {
-                    macs += op_macs(*g, c);
-                    if (b0 == 0) seen[c]++;
-                }
-                macs *= nb;
-                total += macs;
-                if (n < max_records) {
-                    rec_out[4 * n + 0] = k;
-                    rec_out[4 * n + 1] = route;
-                    rec_out[4 * n + 2] = nb;
-                    rec_out[4 * n + 3] = macs;
-                }
-                n++;
-            }
+    mvp::for_each_micro_batch(*g, batch, [&](const mvp::Segment& sg, int64_t, int nb) {
+        for (int l = sg.first_launch; l < sg.end_launch; l++, n++) {
+            const Launch& L = g->launches[l];
+            total += L.macs * nb;
+            if (n >= max_records) continue;
+            const int64_t rec[4] = {L.op, L.route, nb, L.macs * nb};
+            std::copy(rec, rec + 4, rec_out + 4 * n);
         }
-    }
-    for (int k = 0; k < no; k++)
-        MVP_REQUIRE(seen[k] == 1, "mvp_graph_plan: op %d covered by %d launches", k, seen[k]);
+    });
     *n_records = n;
     if (covered_macs_out) *covered_macs_out = total;
     MVP_ABI_END
@@ -1026,10 +888,7 @@ extern "C" int mvp_graph_refresh_weights(void* handle) {
     Graph* g = static_cast<Graph*>(handle);
     MVP_REQUIRE(g != nullptr, "mvp_graph_refresh_weights: NULL handle");
     MVP_HIP(hipDeviceSynchronize());
-    mvp::cat_fill(*g);
-    mvp::sib_fill(*g);
-    mvp::t16_fill(*g);
-    MVP_HIP(hipDeviceSynchronize());
+    mvp::fill_weights(*g);
     MVP_ABI_END
 }
 
@@ -1045,7 +904,7 @@ extern "C" int mvp_graph_destroy(void* handle) {
     Graph* g = static_cast<Graph*>(handle);
     if (g) {
         if (g->arena) (void)hipFree(g->arena);
-        mvp::cat_free(*g);
+        mvp::free_weights(*g);
         delete g;
     }
     MVP_ABI_END
