@@ -696,6 +696,61 @@ int mvp_associate_views(const float* kpts_dev, int T, int P, int J, int V, const
                         uint8_t* out_count_dev, double* out_affinity_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Tracking of people through time: which group of frame t is the person of which group of an
+ * earlier frame, so that a person keeps one number through the recording and through short
+ * dropouts.  No reference counterpart (the reference handles one person per camera).  The input is
+ * what triangulating the groups of the block above gives: per frame G skeletons of J joints in
+ * world units, in no particular order from frame to frame.
+ *
+ * xyz_dev [M][T][G][J][3] float32: M independent sequences of T frames.
+ *   Seen, present: a joint is seen when its three coordinates are finite; group (t, g) is present
+ *     when at least one of its joints is seen.
+ *   Lags: K = max_gap + 1; max_gap is the number of consecutive missing frames a track survives.
+ *   Cost, fp64 from the f32 inputs: for present groups (t, g) and (t − k, h), over the joints seen
+ *     in both, in ascending joint order,
+ *       c = (Σ sqrt(dx² + dy² + dz²)) / count
+ *     defined when count >= min_joints.
+ *   Limit: limit_k = max_jump·(1 + gap_growth·(k − 1)), in fp64 from the two float32 values given.
+ *   Open observation: at frame t, observation (t', h) is open when it is the latest observation of
+ *     its track and t − t' <= K.
+ *   Candidates of frame t: the triples (k, h, g) with 1 <= k <= K, t − k >= 0, (t − k, h) open,
+ *     (t, g) present, c defined and c <= limit_k.
+ *   Linking: the candidates sorted ascending by (c, k, h, g) are taken greedily: a candidate links
+ *     g to the track of (t − k, h) when neither that track nor g has been taken in this frame.
+ *     (k, h) names exactly one track, so the order is total.
+ *   New tracks: the present groups left over start new tracks in ascending g; track numbers count
+ *     up from 0 in order of first appearance.
+ * Consequences: with max_gap = 0 and min_joints = 1 the track numbers are those of frame-to-frame
+ * greedy linking (mvpose.people.link_tracks(xyz, max_jump)).  A track that is not observed for
+ * more than max_gap frames is closed; the person then comes back under a new number.
+ * Arithmetic is fp64 with FMA contraction allowed; no atomics on anything, so the same inputs give
+ * the same bits on every call.  The track numbers and lags equal those of an exact evaluation of
+ * the above whenever every comparison the algorithm makes (a cost against its limit, two
+ * candidates' costs of one frame) has a relative margin above 1e-9.
+ *
+ * mvp_track_people_plan : checks (M, T, G, J, max_gap) as the call does and reports the LDS bytes
+ *   of the kernel's workgroup (one wavefront per sequence, csrc/track.hip; may be NULL):
+ *   (max_gap + 2)·G·(12·J + 4) + (max_gap + 1)·G²·4: a ring of the last K + 1 frames' joints, one
+ *   int32 per (ring slot, group), and one int32 per combination (k, h, g).
+ * mvp_track_people :
+ *   out_track_dev [M][T][G] int32: the group's track number, −1 for an absent group.
+ *   out_n_tracks_dev [M] int32: the number of tracks of each sequence.
+ *   out_link_cost_dev [M][T][G] float64 or NULL: c of the link a group was taken by; NaN for a
+ *     group that starts a track and for an absent group.
+ *   out_link_lag_dev [M][T][G] uint8 or NULL: that link's k; 0 for a new track and for an absent
+ *     group.
+ *   Requires M >= 1, T >= 1, 1 <= G <= 8, 1 <= J <= 255, 0 <= max_gap <= 15, max_jump finite and
+ *   > 0, gap_growth finite and >= 0, 1 <= min_joints <= J, M·T·G·J < 2^31 and the plan's LDS bytes
+ *   <= 65536.  Argument errors return MVP_ERR_ARG before any device work.
+ *   Stream-ordered: one launch, no allocation, no host synchronisation and no decision on the
+ *   host.
+ * ------------------------------------------------------------------------- */
+int mvp_track_people_plan(int M, int T, int G, int J, int max_gap, int* lds_bytes);
+int mvp_track_people(const float* xyz_dev, int M, int T, int G, int J, int max_gap, float max_jump,
+                     float gap_growth, int min_joints, int32_t* out_track_dev, int32_t* out_n_tracks_dev,
+                     double* out_link_cost_dev, uint8_t* out_link_lag_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Bundle adjustment of the extrinsics over the 2D keypoints: R, T of the cameras that may have
  * moved since calibration, the 3D points, and a covariance of the camera unknowns.  No reference
  * counterpart (the reference's extrinsic branch is mvp_sgd_refine_cams: f32, Adam, at most two

@@ -110,6 +110,9 @@ SIGNATURES = {
     "mvp_associate_views": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_float,
                                     c_float, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "mvp_track_people_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_int)]),
+    "mvp_track_people": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_bundle_adjust_plan": (c_int, [c_int64, c_int, ctypes.c_uint, P(c_int64)]),
     "mvp_bundle_adjust_system": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, ctypes.c_uint,
                                          c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_double,

@@ -390,6 +390,47 @@ def associate_views(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[in
     return group, count, aff, pairs
 
 
+def track_people_plan(M: int, T: int, G: int, J: int, max_gap: int = 5) -> int:
+    """The LDS bytes of track_people's workgroup for (M, T, G, J, max_gap) (mvp_track_people_plan,
+    which refuses what the call refuses of these)."""
+    lds = ctypes.c_int(0)
+    call("mvp_track_people_plan", int(M), int(T), int(G), int(J), int(max_gap), ctypes.byref(lds))
+    return lds.value
+
+
+def track_people(xyz: torch.Tensor, *, max_gap: int = 5, max_jump: float = 50.0, gap_growth: float = 0.5,
+                 min_joints: int = 1, return_links: bool = False):
+    """Which group of a frame is the person of which group of an earlier frame
+    (mvp_track_people; the rules are stated in include/mvpose.h; no reference counterpart).
+
+    xyz (T, G, J, 3) or (M, T, G, J, 3) float32 on the GPU: per frame G triangulated skeletons in
+    no particular order, NaN joints allowed, a group with no finite joint is absent; the M
+    sequences are independent.  A group of frame t is linked to the open track whose latest
+    observation, at most max_gap + 1 frames back, is nearest by the mean joint distance over the
+    joints finite in both (at least min_joints of them), greedily in ascending (distance, lag,
+    earlier group, group) while the distance is <= max_jump·(1 + gap_growth·(lag − 1)); a group
+    left over starts a track.  Returns (track (..., T, G) int32, −1 = absent; n_tracks (...) int32
+    on the device; link_cost (..., T, G) float64 and link_lag (..., T, G) uint8 with
+    return_links, else None, None: the distance and the lag of the link a group was taken by, NaN
+    and 0 for a new track or an absent group).  One stream-ordered launch, no workspace."""
+    _require(xyz, torch.float32, "xyz")
+    if xyz.dim() not in (4, 5) or xyz.shape[-1] != 3:
+        raise ValueError(f"xyz must be (T, G, J, 3) or (M, T, G, J, 3), got {tuple(xyz.shape)}")
+    lead = tuple(int(d) for d in xyz.shape[:-2])
+    M, T, G = (1,) + lead if len(lead) == 2 else lead
+    J = int(xyz.shape[-2])
+    track_people_plan(M, T, G, J, max_gap)
+    dev = xyz.device
+    track = torch.empty(lead, dtype=torch.int32, device=dev)
+    n_tracks = torch.empty(lead[:-2], dtype=torch.int32, device=dev)
+    cost = torch.empty(lead, dtype=torch.float64, device=dev) if return_links else None
+    lag = torch.empty(lead, dtype=torch.uint8, device=dev) if return_links else None
+    call("mvp_track_people", _ptr(xyz), M, T, G, J, int(max_gap), float(max_jump), float(gap_growth), int(min_joints),
+         _ptr(track), _ptr(n_tracks), _ptr(cost) if return_links else None, _ptr(lag) if return_links else None,
+         _stream(dev))
+    return track, n_tracks, cost, lag
+
+
 BA_INFO_FIELDS = ("cost_seed", "cost", "trials", "accepted", "status", "lambda", "active_points", "used_views")
 BA_STATUS = {0: "converged", 1: "out of trials", 2: "stalled", 3: "free view observed by fewer than 3 points"}
 

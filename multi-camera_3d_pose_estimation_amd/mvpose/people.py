@@ -6,6 +6,9 @@
   kpts_2d per group.  Torch indexing on the tensors' own device, no host synchronisation.
 * ``link_tracks``: frame-to-frame identity of the triangulated groups, so that
   ops.trajectory_smooth can run per person.
+* ``track_people``: the same identity on the device and through dropouts (ops.track_people).
+* ``person_trajectories``: the per-frame groups re-ordered by track number into one trajectory per
+  person, the layout refine.smooth_trajectory takes.
 """
 from __future__ import annotations
 
@@ -95,3 +98,64 @@ def link_tracks(xyz, max_jump: float = 50.0) -> np.ndarray:
                 track[t, g] = n_tracks
                 n_tracks += 1
     return track
+
+
+def track_people(xyz: torch.Tensor, **kw):
+    """xyz (T, G, J, 3) float32 on the GPU -> (track (T, G) int32 on the device, -1 for an absent
+    group; n_tracks, a 0-dim int32 tensor on the device).  kw: max_gap, max_jump, gap_growth,
+    min_joints of ops.track_people.
+
+    How it differs from link_tracks: it runs on the device in one stream-ordered launch (no copy of
+    xyz to the host, no synchronisation; reading n_tracks as a Python int is the caller's
+    choice), and a track survives up to max_gap (default 5) consecutive frames without an
+    observation: the returning group is linked at lag k to the track's last observation while
+    their distance is <= max_jump·(1 + gap_growth·(k − 1)), so a person occluded for a few frames
+    keeps their number and the gap lies inside one trajectory, where refine.smooth_trajectory can
+    fill it.  link_tracks ends a track at its first missed frame.  With max_gap=0 and
+    min_joints=1 the track numbers are link_tracks' own."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dim() != 4:
+        raise ValueError(f"xyz must be a (T, G, J, 3) tensor, got {tuple(getattr(xyz, 'shape', ()))}")
+    from . import ops
+    track, n_tracks, _, _ = ops.track_people(xyz, **kw)
+    return track, n_tracks
+
+
+def person_trajectories(track: torch.Tensor, arrays: dict, min_len: int = 1, max_people: int | None = None):
+    """track (T, G) integer track numbers (-1 = absent; each number at most once per frame), arrays
+    {name: tensor with leading dimensions (T, G)}, e.g. kpts_3d, kpts_3d_cov, tri_refine_status or
+    the per-group kpts_2d -> (out {name: (T, Np, ...)}, present (T, Np) bool, chosen (Np,) int64).
+
+    The tracks are ranked by the key (-frames present, track number); those present in at least
+    min_len frames are kept, at most max_people of them.  out[name][t, p] is arrays[name][t, g] for
+    the g with track[t, g] == chosen[p]; where person p is absent it is NaN for floating-point
+    arrays and 0 for integer and bool ones.  Torch indexing on track's own device, as
+    gather_groups; ranking the tracks by length takes one small device-to-host read, of the
+    per-track frame counts (torch.bincount also reads the largest track number to size them)."""
+    if not isinstance(track, torch.Tensor) or track.dim() != 2 or track.dtype.is_floating_point:
+        raise ValueError("track must be a (T, G) integer tensor")
+    T, G = track.shape
+    for name, a in arrays.items():
+        if not isinstance(a, torch.Tensor) or tuple(a.shape[:2]) != (T, G):
+            raise ValueError(f"arrays[{name!r}] must be a tensor with leading dimensions {(T, G)}")
+    if min_len < 1 or (max_people is not None and max_people < 0):
+        raise ValueError(f"min_len={min_len} must be >= 1 and max_people={max_people} >= 0")
+    dev = track.device
+    tr = track.to(torch.int64)
+    counts = torch.bincount((tr.clamp(min=-1) + 1).reshape(-1))[1:].cpu().numpy()      # the one host read
+    order = sorted((i for i in range(len(counts)) if counts[i] >= min_len), key=lambda i: (-int(counts[i]), i))
+    if max_people is not None:
+        order = order[:int(max_people)]
+    chosen = torch.tensor(order, dtype=torch.int64, device=dev)
+    match = tr[:, :, None] == chosen[None, None, :]                      # (T, G, Np)
+    present = match.any(1)
+    g_of = match.to(torch.int8).argmax(1) if G > 0 and len(order) else torch.zeros((T, len(order)), dtype=torch.int64,
+                                                                                  device=dev)
+    rows = torch.arange(T, device=dev)[:, None]
+    out = {}
+    for name, a in arrays.items():
+        a = a.to(dev)
+        got = a[rows, g_of]                                              # (T, Np, ...)
+        fill = float("nan") if a.dtype.is_floating_point else 0
+        keep = present.reshape(present.shape + (1,) * (a.dim() - 2))
+        out[name] = torch.where(keep, got, torch.full((), fill, dtype=a.dtype, device=dev))
+    return out, present, chosen

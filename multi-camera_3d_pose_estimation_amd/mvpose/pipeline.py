@@ -12,7 +12,9 @@ tri_refine_status come with it (ops.triangulate_refine).
 
 process_people(frames, bboxes (T, V, P, 4)) is the same path for several people per camera (no
 reference counterpart): the 2D stage per person box, ops.associate_views across the cameras, then
-one kpts_2d / kpts_3d per group of skeletons that show the same person.
+one kpts_2d / kpts_3d per group of skeletons that show the same person.  Group numbers are per
+frame; people_trajectories(out) tracks the groups through time (ops.track_people) and returns one
+trajectory per person.
 
 process(..., overlap_moments=True) computes heatmaps_2d on a side stream beside the
 next batch's backbone (triangulation reads only kpts_2d); call wait(out) before reading
@@ -225,6 +227,33 @@ class MultiViewPipeline:
             out["tri_refine_cost"] = cost.reshape(T, G, N_JOINTS)
             out["tri_refine_status"] = status.reshape(T, G, N_JOINTS)
         return out
+
+    @staticmethod
+    def people_trajectories(out: dict, min_len: int = 1, max_people: int | None = None, **track_kw) -> dict:
+        """One trajectory per person from a process_people result, or from the concatenation along
+        time of several chunks' results (group numbers are per frame; this is what gives a person
+        one number through the recording).  people.track_people on kpts_3d (track_kw: max_gap,
+        max_jump, gap_growth, min_joints), then people.person_trajectories (min_len, max_people).
+        Returns, device-resident, people ordered by (-frames present, track number):
+            kpts_3d_person   (T, Np, 17, 3) float32   NaN where the person is absent
+            person_present   (T, Np) bool
+            person_track     (Np,) int64              the tracker's number of each person
+        and, when out carries them (refine=), kpts_3d_cov_person (T, Np, 17, 3, 3) and
+        tri_refine_status_person (T, Np, 17) uint8 (0 where absent; the NaN points mark those
+        frames).  refine.smooth_trajectory takes person p as kpts_3d_person[:, p],
+        cov=kpts_3d_cov_person[:, p], status=tri_refine_status_person[:, p], and fills the frames
+        the person was not seen in."""
+        from . import people
+        xyz = out["kpts_3d"]
+        if xyz.dim() != 4 or xyz.shape[3] != 3:
+            raise ValueError(f"out['kpts_3d'] must be (T, G, J, 3) as process_people returns it, got {tuple(xyz.shape)}")
+        track, _ = people.track_people(xyz.contiguous(), **track_kw)
+        arrays = {k: out[k] for k in ("kpts_3d", "kpts_3d_cov", "tri_refine_status") if k in out}
+        got, present, chosen = people.person_trajectories(track, arrays, min_len=min_len, max_people=max_people)
+        res = {k + "_person": v for k, v in got.items()}
+        res["person_present"] = present
+        res["person_track"] = chosen
+        return res
 
     @staticmethod
     def wait(out: dict) -> None:
