@@ -839,6 +839,93 @@ int mvp_bundle_adjust(const float* kpts_dev, int64_t n_points, int V, const doub
                       uint8_t* out_point_status_dev, double* out_cam_cov_dev, double* out_info_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Trajectories fitted to the 2D keypoints, so that a frame seen by a single view still counts.  No
+ * reference counterpart: the reference's SGD refinement (mvp_sgd_refine) scores every camera's
+ * pixels against the trajectory plus the same second-difference cost, but in f32 with Adam over
+ * thousands of steps, with no per-view mask, no robust loss and no weights of the view's own.
+ * triangulate -> smooth needs two usable views of a joint in a frame; on a two-camera rig one
+ * camera losing a joint removes it from 3D, and mvp_trajectory_smooth fills the gap from its ends
+ * alone, although the camera that still sees the joint fixes two of its three coordinates.
+ *
+ * kpts_dev [T][P][3][V] float32: for one person the kpts_2d layout with P = J; several people are
+ * concatenated along that axis.  Chains p are independent; chain p has unknowns X_t in R³,
+ * t = 0..T-1.  cams_dev, cam_idx_host / n_cam_idx (2..8) as for mvp_triangulate_refine.
+ *   Used view, observation z_i, weight W_i, forward model pi_i: exactly mvp_triangulate_refine's
+ *     rules for point (t, p): mask_dev [T][P] uint8 (bit i: view i may be used) or NULL, min_conf,
+ *     the three MVP_REFINE_W_* modes, gauss_dev [T][V][P][6] float64 (required for
+ *     MVP_REFINE_W_GAUSS), cov_floor.  The used set depends on the keypoints alone and is the same
+ *     at every state.  nviews(t, p) is its size.
+ *   rho, omega: exactly mvp_bundle_adjust's Huber loss on the whitened residual s = sqrt(rᵀ·W·r),
+ *     r = pi_i(X_t) - z_i: rho = ½s² when huber_delta <= 0 or s <= delta, else delta·(s - ½delta);
+ *     omega = 1 or delta/s; W~ = omega·W.
+ *   Valid chain: its seed is finite in every frame; every used view has P_z > 0 at the seed; at
+ *     least 2 frames have at least 2 used views (that pins the affine-in-t null space of the
+ *     prior); the cost at the seed is finite.  An invalid chain returns its seed's bits as
+ *     out_xyz (NaNs included), NaN resid and cost, and status 0x80.
+ *   Cost per chain:
+ *       f(X) = Σ_t Σ_used rho  +  ½ λ Σ_{t=2}^{T-1} |X_t - 2 X_{t-1} + X_{t-2}|²
+ *     and +inf when a used view has P_z <= 0.  λ = lambda_smooth in 1 / (world unit)²  per pixel-
+ *     weight unit: with unit weights the data term is in pixels², so λ = (σ_px / σ_a)², σ_a the
+ *     standard deviation of a joint's second difference per frame in world units.
+ *   Linearisation at a state: per frame H~_t = Σ_used Jᵀ W~ J (3x3) and g~_t = Σ_used Jᵀ W~ r,
+ *     J = d pi_i / dX.  With D₂ the (T-2)xT second-difference matrix,
+ *       A = blockdiag(H~) + λ·(D₂ᵀD₂ ⊗ I₃),    G = g~ + λ·(D₂ᵀD₂ ⊗ I₃)·X.
+ *     A frame with one used view contributes its rank-2 block, a frame with none contributes
+ *     nothing and is carried by the prior.
+ *   Solver, per chain: Levenberg-Marquardt, mu = 1e-3 at the start.  A trial solves
+ *     (A + mu·diag A)·d = -G (block-pentadiagonal, by the partition method of
+ *     mvp_trajectory_smooth; chunk as there) and forms X + d.  It is accepted when f(X + d) is
+ *     finite and <= f: the state becomes X + d and mu <- max(0.1·mu, 1e-12); otherwise
+ *     mu <- 10·mu.  A pivot of the solve that is not > 0 (NaN included) is a rejected trial.  The
+ *     run stops: converged (status bit 0x40 clear) at the first accepted trial with
+ *     f - f(trial) <= tol·f; stalled (0x40) when mu > 1e12; out of trials (0x40) after max_iter
+ *     (0..63) trials — tested in this order after each trial.  Status bits 0-5 hold the number of
+ *     trials.  With max_iter = 0 the call returns the seed with the cost evaluated there (0x40).
+ * Everything is fp64 on the device from the float32 inputs, FMA contraction allowed (no bit
+ * contract against another implementation).  No floating-point atomics: a chain's cost is summed
+ * per tile of 256 frames in a fixed order and the tiles in ascending order, so the same inputs give
+ * the same bits on every call.  The result does not depend on chunk beyond fp64 rounding.
+ * Long stretches seen by one view only: the depth along that view's rays is then held by the prior
+ * alone, and with a weak prior (small λ) it wanders: over tens of frames the fit can be worse than
+ * the smoother's blind interpolation.  Such recordings need a stiffer prior (larger λ).
+ *
+ * mvp_trajectory_fit_plan : what a call with (T, P, chunk) will use: the chunk length, the chunks
+ *   per chain and the bytes of the caller-owned workspace (contents are scratch); any may be NULL.
+ * mvp_trajectory_fit_system : ONE linearisation of the data term at the given float32 trajectory
+ *   xyz_dev [T][P][3]; no solve, no state, no validity test.  out_H_dev [T][P][6] float64 (xx, xy,
+ *   xz, yy, yz, zz) and out_g_dev [T][P][3] float64: H~_t and g~_t (a used view behind its camera
+ *   contributes what the arithmetic gives; a frame that is not finite gives NaN);
+ *   out_nviews_dev [T][P] uint8; out_cost_dev [P][2] float64: {Σ rho (+inf behind a camera), the
+ *   smoothness term with λ = 1, i.e. ½ Σ |second difference|²}.  All four are required.
+ * mvp_trajectory_fit : the whole optimisation from the seed xyz0_dev [T][P][3] float32,
+ *   stream-ordered, with no host synchronisation, no allocation and no decision on the host: the
+ *   number of launches is fixed by max_iter, and a per-chain flag in the workspace makes the lanes
+ *   of a finished chain return at once.
+ *   out_xyz_dev [T][P][3] float32; out_resid_dev [T][P] float32 or NULL: Σ_used s² (not rho) at
+ *   the final state, NaN when nviews = 0 and for invalid chains; out_nviews_dev [T][P] uint8 or
+ *   NULL; out_cost_dev [P][2] float64 or NULL: f at the seed and at the final state;
+ *   out_status_dev [P] uint8 or NULL.
+ * Requires T >= 1, P >= 1, T·P < 2^31, 2 <= n_cam_idx <= 8, lambda_smooth and tol finite and > 0,
+ * cov_floor >= 0, min_conf and huber_delta not NaN (huber_delta <= 0: off), 0 <= max_iter <= 63,
+ * chunk = 0 or 4..4096.  Argument errors return MVP_ERR_ARG before any device work.
+ * Out of scope: a posterior covariance of the trajectory (it needs the selected inverse of A, not
+ * a solve); sub-frame time offsets between the cameras (mvp_epipolar_lag_cost finds whole frames);
+ * coupling between chains such as bone lengths (chains stay independent).
+ * ------------------------------------------------------------------------- */
+int mvp_trajectory_fit_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_trajectory_fit_system(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                              const int* cam_idx_host, int n_cam_idx, const float* xyz_dev, const uint8_t* mask_dev,
+                              int weights, const double* gauss_dev, float min_conf, float cov_floor,
+                              double huber_delta, double* out_H_dev, double* out_g_dev, uint8_t* out_nviews_dev,
+                              double* out_cost_dev, void* stream);
+int mvp_trajectory_fit(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                       const int* cam_idx_host, int n_cam_idx, const float* xyz0_dev, const uint8_t* mask_dev,
+                       int weights, const double* gauss_dev, float min_conf, float cov_floor, double huber_delta,
+                       double lambda_smooth, int max_iter, double tol, int chunk, void* workspace_dev,
+                       int64_t workspace_bytes, float* out_xyz_dev, float* out_resid_dev, uint8_t* out_nviews_dev,
+                       double* out_cost_dev, uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's
  * recordings (utils.py:849-909 read_video_as_frames; synchronize_videos.py:64,240 writes them with
  * cv2.VideoWriter_fourcc(*'mp4v')).  Simple Profile: I / P-VOPs, video packets, H.263 or MPEG

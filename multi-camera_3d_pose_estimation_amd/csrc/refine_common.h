@@ -120,6 +120,52 @@ __device__ __forceinline__ bool refine_view_terms(const RefineCam& c, const doub
     return w.Pz > 0;
 }
 
+// refine_view_terms with a Huber loss on the whitened residual s = sqrt(rᵀ·W·r), the rho and the
+// IRLS weight omega of mvp_bundle_adjust (hub <= 0: off): rho and s² are added to their sums, and
+// with JAC g += Jᵀ·W̃·r, H += Jᵀ·W̃·J, W̃ = omega·W.  Branch-free; false when the point is not in
+// front of the camera.
+template <bool JAC>
+__device__ __forceinline__ bool refine_view_terms_huber(const RefineCam& c, const double (&X)[3], double zx, double zy,
+                                                        double wxx, double wxy, double wyy, double hub, double& rho,
+                                                        double& s2sum, double (&g)[3], double (&H)[6]) {
+#pragma clang fp contract(fast)
+    const RefineFwd w = refine_forward(c, X);
+    const double r0 = w.u - zx;
+    const double r1 = w.v - zy;
+    const double s2 = r0 * (wxx * r0 + wxy * r1) + r1 * (wxy * r0 + wyy * r1);
+    const double s = sqrt(s2);
+    const bool quad = !(hub > 0) || !(s > hub);
+    const double om = quad ? 1.0 : hub / s;
+    rho += quad ? 0.5 * s2 : hub * (s - 0.5 * hub);
+    s2sum += s2;
+    if (JAC) {
+        const double oxx = om * wxx, oxy = om * wxy, oyy = om * wyy;
+        double J0[3], J1[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const double m0 = (c.R[k] - w.x * c.R[6 + k]) * w.iz;  // d x / d X_k
+            const double m1 = (c.R[3 + k] - w.y * c.R[6 + k]) * w.iz;
+            J0[k] = w.a00 * m0 + w.a01 * m1;
+            J1[k] = w.a10 * m0 + w.a11 * m1;
+        }
+        const double wr0 = oxx * r0 + oxy * r1, wr1 = oxy * r0 + oyy * r1;
+        double wj0[3], wj1[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            wj0[k] = oxx * J0[k] + oxy * J1[k];
+            wj1[k] = oxy * J0[k] + oyy * J1[k];
+            g[k] += J0[k] * wr0 + J1[k] * wr1;
+        }
+        H[0] += J0[0] * wj0[0] + J1[0] * wj1[0];
+        H[1] += J0[0] * wj0[1] + J1[0] * wj1[1];
+        H[2] += J0[0] * wj0[2] + J1[0] * wj1[2];
+        H[3] += J0[1] * wj0[1] + J1[1] * wj1[1];
+        H[4] += J0[1] * wj0[2] + J1[1] * wj1[2];
+        H[5] += J0[2] * wj0[2] + J1[2] * wj1[2];
+    }
+    return w.Pz > 0;
+}
+
 // Cholesky A = L·Lᵀ of the symmetric 3x3 (xx, xy, xz, yy, yz, zz); false on a non-positive (or
 // NaN) pivot.  L: l00, l10, l20, l11, l21, l22.
 __device__ __forceinline__ bool chol3(const double (&A)[6], double (&L)[6]) {

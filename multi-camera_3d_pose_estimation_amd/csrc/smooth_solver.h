@@ -1,0 +1,518 @@
+// The partition solver of the block-pentadiagonal chain systems (3x3 blocks), shared by the
+// trajectory smoother (smooth.hip) and the trajectory fit (trajectory_fit.hip).  The algorithm,
+// the workspace layout and the three sweeps (eliminate, reduce, backsub) are described at the top
+// of smooth.hip; this header holds the per-lane code, templated on the frame source A:
+//
+//   A has the fields of SolveCore (by derivation or by name) and adds
+//     Raw / Out                     what load_raw / load_out return (requested one step ahead)
+//     kInfoForm                     false: frame_weight gives (W, z) and the rhs is W z;
+//                                   true: it gives (W, b) in information form, the rhs is b
+//     damp(p)                       the Marquardt factor (1 + mu_p) of the diagonal entries, or NoDamp
+//     skip(p)                       the chain takes no part in this call (its lanes return)
+//     load_raw(t, p), frame_weight(raw, W, z)     the eliminate sweep's frame
+//     load_out(t, p), write_frame(t, p, out, x0, x1, x2), failed(p), write_failed(t, p)   backsub
+//     finish(p, cnt, bad)           the end of the reduce: per-chain status
+//
+// The per-lane functions also compile for the host, where a CPU build can step through them.
+#pragma once
+// FMA contraction is allowed in everything below, whatever an earlier header left in force
+// (refine_common.h turns it off at file scope).
+#pragma clang fp contract(fast)
+#include "mvp_common.h"
+
+#include <cmath>
+#include <cstdint>
+
+#define MVP_SMOOTH_HD __host__ __device__ __forceinline__
+
+namespace {
+
+constexpr int kSmBlock = 64;         // threads per block: few lanes exist (P·n_chunks), spread them over CUs
+constexpr int kFacDoubles = 39;      // per eliminated frame: G (12x3) | q (3)
+constexpr int kSchurDoubles = 90;    // per lane: lower triangle of the 12x12 Schur complement (78) | rhs (12)
+constexpr int kRedDoubles = 63;      // per separator and chain: C (21, lower, 1/diagonal) | Y (36) | y (6)
+constexpr int kMinChunk = 4, kMaxChunk = 4096;
+
+// What the three sweeps need whatever the frames come from.
+struct SolveCore {
+    int T, P, chunk, n_chunks, n_seps;
+    int64_t n_lanes, n_blocks;
+    double lambda;
+    double* fac;    // [step][block][39][64]
+    double* schur;  // [block][90][64]
+    double* red;    // [sep][63][P]
+    double* usol;   // [sep][6][P]
+    int* cnt;       // [P] observed frames (zeroed before the eliminate launch)
+    int* bad;       // [P] a pivot was not > 0 (zeroed likewise)
+};
+
+MVP_SMOOTH_HD constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
+
+// 1/sqrt(s), s > 0 and normal, to ~1 ulp: v_rsq_f64 + two Newton steps on the device (a sixth of
+// the instructions of an fp64 sqrt followed by an fp64 division; every sweep step has six of them
+// on its critical path).
+MVP_SMOOTH_HD double inv_sqrt(double s) {
+#ifdef __HIP_DEVICE_COMPILE__
+    double y = __builtin_amdgcn_rsq(s);
+    double t = s * y;
+    double e = __builtin_fma(-t, y, 1.0);
+    y = __builtin_fma(0.5 * y, e, y);
+    t = s * y;
+    e = __builtin_fma(-t, y, 1.0);
+    return __builtin_fma(0.5 * y, e, y);
+#else
+    return 1.0 / sqrt(s);
+#endif
+}
+
+// Inverse of the symmetric 3x3 s = (xx, xy, xz, yy, yz, zz) by Cholesky; false unless all three
+// pivots are > 0 (NaN included).
+MVP_SMOOTH_HD bool spd3_inverse(const double (&s)[6], double (&w)[6]) {
+    const double d0 = s[0];
+    const bool ok0 = d0 > 0;
+    const double i00 = inv_sqrt(ok0 ? d0 : 1.0);
+    const double l10 = s[1] * i00, l20 = s[2] * i00;
+    const double d1 = s[3] - l10 * l10;
+    const bool ok1 = d1 > 0;
+    const double i11 = inv_sqrt(ok1 ? d1 : 1.0);
+    const double l21 = (s[4] - l20 * l10) * i11;
+    const double d2 = s[5] - l20 * l20 - l21 * l21;
+    const bool ok2 = d2 > 0;
+    const double i22 = inv_sqrt(ok2 ? d2 : 1.0);
+    // L⁻¹, then W = L⁻ᵀ L⁻¹
+    const double i10 = -l10 * i00 * i11;
+    const double i21 = -l21 * i11 * i22;
+    const double i20 = -(l20 * i00 + l21 * i10) * i22;
+    w[0] = i00 * i00 + i10 * i10 + i20 * i20;
+    w[1] = i10 * i11 + i20 * i21;
+    w[2] = i20 * i22;
+    w[3] = i11 * i11 + i21 * i21;
+    w[4] = i21 * i22;
+    w[5] = i22 * i22;
+    return ok0 && ok1 && ok2;
+}
+
+// Workspace addressing: lanes in blocks of kSmBlock (one wave), [element][lane of the block] inside.
+template <class A>
+MVP_SMOOTH_HD int64_t fac_index(const A& a, int step, int64_t lane) {
+    return (((int64_t)step * a.n_blocks + lane / kSmBlock) * kFacDoubles) * kSmBlock + lane % kSmBlock;
+}
+MVP_SMOOTH_HD int64_t schur_index(int64_t lane) {
+    return (lane / kSmBlock) * kSchurDoubles * kSmBlock + lane % kSmBlock;
+}
+
+// The Marquardt factor of a diagonal entry: a compile-time 1 for a source that has none.
+struct NoDamp {};
+MVP_SMOOTH_HD double damped(double v, NoDamp) { return v; }
+MVP_SMOOTH_HD double damped(double v, double damp) { return v * damp; }
+
+// Data term of the frame in window block B: W onto its diagonal block (its diagonal entries times
+// the Marquardt factor), and onto its rhs W z, or z itself when the source is in information form.
+template <int B, bool INFO, class D>
+MVP_SMOOTH_HD void add_data(double (&M)[120], double (&r)[15], const double (&W)[6], const double (&z)[3], D damp) {
+    constexpr int o = 3 * B;
+    M[tri(o, o)] += damped(W[0], damp);
+    M[tri(o + 1, o)] += W[1];
+    M[tri(o + 2, o)] += W[2];
+    M[tri(o + 1, o + 1)] += damped(W[3], damp);
+    M[tri(o + 2, o + 1)] += W[4];
+    M[tri(o + 2, o + 2)] += damped(W[5], damp);
+    if (INFO) {
+        r[o] += z[0];
+        r[o + 1] += z[1];
+        r[o + 2] += z[2];
+    } else {
+        r[o] += W[0] * z[0] + W[1] * z[1] + W[2] * z[2];
+        r[o + 1] += W[1] * z[0] + W[3] * z[1] + W[4] * z[2];
+        r[o + 2] += W[2] * z[0] + W[4] * z[1] + W[5] * z[2];
+    }
+}
+
+// λ v vᵀ ⊗ I₃ with v = (1, −2, 1) on window blocks B, B+1, B+2: one second-difference row (its
+// diagonal entries times the Marquardt factor).
+template <int B, class D>
+MVP_SMOOTH_HD void add_element(double (&M)[120], double lam, D damp) {
+    constexpr double v[3] = {1.0, -2.0, 1.0};
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j <= i; j++)
+#pragma unroll
+            for (int d = 0; d < 3; d++)
+                M[tri(3 * (B + i) + d, 3 * (B + j) + d)] += i == j ? damped(lam * v[i] * v[j], damp) : lam * v[i] * v[j];
+}
+
+// The frames lane (chain p, chunk k) works on.
+struct LaneRange {
+    int p, k;
+    int g0;  // first interior frame
+    int n;   // interior frames (>= 1)
+    int hi;  // end of the owned frames: interior + right separator (0, 1 or 2 frames)
+};
+
+template <class A>
+MVP_SMOOTH_HD LaneRange lane_range(const A& a, int64_t lane) {
+    LaneRange r;
+    r.k = (int)(lane / a.P);
+    r.p = (int)(lane - (int64_t)r.k * a.P);
+    r.g0 = r.k * (a.chunk + 2);
+    const int left = a.T - r.g0;
+    r.n = left < a.chunk ? left : a.chunk;
+    const int own = left < a.chunk + 2 ? left : a.chunk + 2;
+    r.hi = r.g0 + own;
+    return r;
+}
+
+// Window rows: 0..5 left separator (frames g0-2, g0-1), 6..8 frame a, 9..11 frame b, 12..14 frame c.
+template <class A>
+MVP_SMOOTH_HD void eliminate_lane(const A& a, int64_t lane) {
+    const LaneRange R = lane_range(a, lane);
+    if (a.skip(R.p)) return;
+    const auto damp = a.damp(R.p);
+    double M[120], r[15];
+#pragma unroll
+    for (int i = 0; i < 120; i++) M[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 15; i++) r[i] = 0.0;
+    int cnt = 0;
+    bool bad = false;
+    double W[6], z[3];
+    const bool has_b = R.g0 + 1 < R.hi;
+    const typename A::Raw fa = a.load_raw(R.g0, R.p);
+    const typename A::Raw fb = a.load_raw(has_b ? R.g0 + 1 : R.g0, R.p);
+    typename A::Raw nxt = a.load_raw(R.g0 + 2 < R.hi ? R.g0 + 2 : R.g0, R.p);
+    cnt += a.frame_weight(fa, W, z);
+    add_data<2, A::kInfoForm>(M, r, W, z, damp);
+    if (has_b) {
+        cnt += a.frame_weight(fb, W, z);
+        add_data<3, A::kInfoForm>(M, r, W, z, damp);
+    }
+    if (R.k > 0) {
+        add_element<0>(M, a.lambda, damp);
+        if (has_b) add_element<1>(M, a.lambda, damp);
+    }
+    for (int i = 0; i < R.n; i++) {
+        // frame c enters; the frame after it is requested now
+        const int c = R.g0 + i + 2;
+        const typename A::Raw fc = nxt;
+        if (c + 1 < R.hi) nxt = a.load_raw(c + 1, R.p);
+#pragma unroll
+        for (int j = tri(12, 0); j < 120; j++) M[j] = 0.0;
+        r[12] = r[13] = r[14] = 0.0;
+        if (c < R.hi) {
+            cnt += a.frame_weight(fc, W, z);
+            add_data<4, A::kInfoForm>(M, r, W, z, damp);
+            add_element<2>(M, a.lambda, damp);
+        }
+        // frame a leaves: pivot P = M[a][a]
+        const double s[6] = {M[tri(6, 6)], M[tri(7, 6)], M[tri(8, 6)], M[tri(7, 7)], M[tri(8, 7)], M[tri(8, 8)]};
+        double Pi[6];
+        bad = !spd3_inverse(s, Pi) || bad;
+        const double q0 = Pi[0] * r[6] + Pi[1] * r[7] + Pi[2] * r[8];
+        const double q1 = Pi[1] * r[6] + Pi[3] * r[7] + Pi[4] * r[8];
+        const double q2 = Pi[2] * r[6] + Pi[4] * r[7] + Pi[5] * r[8];
+        double* f = a.fac + fac_index(a, i, lane);
+        double C[12][3], G[12][3];
+#pragma unroll
+        for (int o = 0; o < 12; o++) {
+            const int row = o < 6 ? o : o + 3;
+#pragma unroll
+            for (int d = 0; d < 3; d++) C[o][d] = row < 6 ? M[tri(6 + d, row)] : M[tri(row, 6 + d)];
+            G[o][0] = C[o][0] * Pi[0] + C[o][1] * Pi[1] + C[o][2] * Pi[2];
+            G[o][1] = C[o][0] * Pi[1] + C[o][1] * Pi[3] + C[o][2] * Pi[4];
+            G[o][2] = C[o][0] * Pi[2] + C[o][1] * Pi[4] + C[o][2] * Pi[5];
+#pragma unroll
+            for (int d = 0; d < 3; d++) f[(3 * o + d) * kSmBlock] = G[o][d];
+        }
+        f[36 * kSmBlock] = q0;
+        f[37 * kSmBlock] = q1;
+        f[38 * kSmBlock] = q2;
+        // Schur update of the 12 remaining rows, shifted into place: rows 9..14 move to 6..11
+#pragma unroll
+        for (int o = 0; o < 12; o++) {
+            const int row = o < 6 ? o : o + 3;
+#pragma unroll
+            for (int u = 0; u <= o; u++) {
+                const int col = u < 6 ? u : u + 3;
+                M[tri(o, u)] = M[tri(row, col)] - (G[o][0] * C[u][0] + G[o][1] * C[u][1] + G[o][2] * C[u][2]);
+            }
+            r[o] = r[row] - (C[o][0] * q0 + C[o][1] * q1 + C[o][2] * q2);
+        }
+    }
+    // the window's first 12 rows are now (left separator, right separator); a separator frame past
+    // the end of the recording is decoupled: give it a unit diagonal so the reduced block stays SPD
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+        if (R.g0 + R.n + q >= a.T)
+#pragma unroll
+            for (int d = 0; d < 3; d++) M[tri(6 + 3 * q + d, 6 + 3 * q + d)] = 1.0;
+    double* sc = a.schur + schur_index(lane);
+#pragma unroll
+    for (int i = 0; i < 78; i++) sc[i * kSmBlock] = M[i];
+#pragma unroll
+    for (int i = 0; i < 12; i++) sc[(78 + i) * kSmBlock] = r[i];
+#ifdef __HIP_DEVICE_COMPILE__
+    if (cnt) atomicAdd(&a.cnt[R.p], cnt);
+    if (bad) atomicOr(&a.bad[R.p], 1);
+#else
+    a.cnt[R.p] += cnt;
+    a.bad[R.p] |= bad ? 1 : 0;
+#endif
+}
+
+// What the reduce phase reads for separator j of chain p, 90 doubles: the right-separator corner
+// of chunk j's Schur complement (21) and rhs (6), the left-separator corner of chunk j+1's (21)
+// and rhs (6), and E (36), the coupling to separator j+1 (row: coordinate of j, column: of j+1).
+constexpr int kInRR = 0, kInGR = 21, kInLL = 27, kInGL = 48, kInE = 54, kInDoubles = 90;
+
+template <class A>
+MVP_SMOOTH_HD void load_reduce_in(const A& a, int p, int j, double (&v)[kInDoubles]) {
+    const double* s0 = a.schur + schur_index((int64_t)j * a.P + p);
+    const bool has_next = j + 1 < a.n_chunks, has_e = j + 1 < a.n_seps;
+    const double* s1 = a.schur + schur_index((int64_t)(has_next ? j + 1 : j) * a.P + p);
+#pragma unroll
+    for (int i = 0; i < 6; i++) {
+#pragma unroll
+        for (int u = 0; u <= i; u++) {
+            v[kInRR + tri(i, u)] = s0[tri(6 + i, 6 + u) * kSmBlock];
+            v[kInLL + tri(i, u)] = has_next ? s1[tri(i, u) * kSmBlock] : 0.0;
+        }
+        v[kInGR + i] = s0[(78 + 6 + i) * kSmBlock];
+        v[kInGL + i] = has_next ? s1[(78 + i) * kSmBlock] : 0.0;
+#pragma unroll
+        for (int u = 0; u < 6; u++) v[kInE + 6 * i + u] = has_e ? s1[tri(6 + u, i) * kSmBlock] : 0.0;
+    }
+}
+
+// One chain's reduced system, forward then back, everything in registers (fully unrolled; the
+// 6x6 blocks are packed lower triangles).
+template <class A>
+MVP_SMOOTH_HD void reduce_chain(const A& a, int p) {
+    if (a.skip(p)) return;
+    int bad = a.bad[p];
+    const int ns = a.n_seps;
+    double in[kInDoubles];
+    double Yp[36], yp[6];   // Y, y of separator j-1 (0 in front of the first)
+#pragma unroll
+    for (int i = 0; i < 36; i++) Yp[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) yp[i] = 0.0;
+    if (ns > 0) load_reduce_in(a, p, 0, in);
+    for (int j = 0; j < ns; j++) {
+        // D = right-separator part of chunk j + left-separator part of chunk j+1 - Yᵀ Y of separator j-1
+        double D[21], g[6], Y[36];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+#pragma unroll
+            for (int u = 0; u <= i; u++) {
+                double d = in[kInRR + tri(i, u)] + in[kInLL + tri(i, u)];
+#pragma unroll
+                for (int m = 0; m < 6; m++) d -= Yp[6 * m + i] * Yp[6 * m + u];
+                D[tri(i, u)] = d;
+            }
+            double e = in[kInGR + i] + in[kInGL + i];
+#pragma unroll
+            for (int m = 0; m < 6; m++) e -= Yp[6 * m + i] * yp[m];
+            g[i] = e;
+        }
+#pragma unroll
+        for (int i = 0; i < 36; i++) Y[i] = in[kInE + i];
+        if (j + 1 < ns) load_reduce_in(a, p, j + 1, in);   // requested now, used in the next step
+        // Cholesky D = C Cᵀ in place; the diagonal keeps 1 / C_ii
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+#pragma unroll
+            for (int u = 0; u <= i; u++) {
+                double d = D[tri(i, u)];
+#pragma unroll
+                for (int m = 0; m < u; m++) d -= D[tri(i, m)] * D[tri(u, m)];
+                if (u < i) {
+                    D[tri(i, u)] = d * D[tri(u, u)];
+                } else {
+                    const bool ok = d > 0;
+                    bad = ok ? bad : 1;
+                    D[tri(i, i)] = inv_sqrt(ok ? d : 1.0);
+                }
+            }
+        }
+        // Y = C⁻¹ E, y = C⁻¹ g
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+#pragma unroll
+            for (int u = 0; u < 6; u++) {
+                double d = Y[6 * i + u];
+#pragma unroll
+                for (int m = 0; m < i; m++) d -= D[tri(i, m)] * Y[6 * m + u];
+                Y[6 * i + u] = d * D[tri(i, i)];
+            }
+            double e = g[i];
+#pragma unroll
+            for (int m = 0; m < i; m++) e -= D[tri(i, m)] * g[m];
+            g[i] = e * D[tri(i, i)];
+        }
+        double* rd = a.red + ((int64_t)j * kRedDoubles) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < 21; i++) rd[(int64_t)i * a.P] = D[i];
+#pragma unroll
+        for (int i = 0; i < 36; i++) {
+            rd[(int64_t)(21 + i) * a.P] = Y[i];
+            Yp[i] = Y[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            rd[(int64_t)(57 + i) * a.P] = g[i];
+            yp[i] = g[i];
+        }
+    }
+    // back: u_j = C⁻ᵀ (y − Y u_{j+1}), in registers, separator j-1's factor requested while j is solved
+    double u[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double cur[kRedDoubles], nxt[kRedDoubles];
+    if (ns > 0) {
+        const double* rd = a.red + ((int64_t)(ns - 1) * kRedDoubles) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < kRedDoubles; i++) cur[i] = rd[(int64_t)i * a.P];
+    }
+    for (int j = ns - 1; j >= 0; j--) {
+        if (j > 0) {
+            const double* rd = a.red + ((int64_t)(j - 1) * kRedDoubles) * a.P + p;
+#pragma unroll
+            for (int i = 0; i < kRedDoubles; i++) nxt[i] = rd[(int64_t)i * a.P];
+        }
+        double v[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            double d = cur[57 + i];
+#pragma unroll
+            for (int m = 0; m < 6; m++) d -= cur[21 + 6 * i + m] * u[m];
+            v[i] = d;
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; i--) {
+            double d = v[i];
+#pragma unroll
+            for (int m = i + 1; m < 6; m++) d -= cur[tri(m, i)] * u[m];
+            u[i] = d * cur[tri(i, i)];
+        }
+        double* us = a.usol + ((int64_t)j * 6) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < 6; i++) us[(int64_t)i * a.P] = u[i];
+        if (j > 0) {
+#pragma unroll
+            for (int i = 0; i < kRedDoubles; i++) cur[i] = nxt[i];
+        }
+    }
+    a.finish(p, a.cnt[p], bad);
+}
+
+template <class A>
+MVP_SMOOTH_HD void backsub_lane(const A& a, int64_t lane) {
+    const LaneRange R = lane_range(a, lane);
+    if (a.skip(R.p)) return;
+    if (a.failed(R.p)) {
+        for (int t = R.g0; t < R.hi; t++) a.write_failed(t, R.p);
+        return;
+    }
+    // x: 0..5 left separator, 6..11 frames b, c (the right separator to start with)
+    double x[12];
+#pragma unroll
+    for (int i = 0; i < 12; i++) x[i] = 0.0;
+    if (R.k > 0) {
+        const double* us = a.usol + ((int64_t)(R.k - 1) * 6) * a.P + R.p;
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[i] = us[(int64_t)i * a.P];
+    }
+    if (R.k < a.n_seps) {
+        const double* us = a.usol + ((int64_t)R.k * 6) * a.P + R.p;
+#pragma unroll
+        for (int i = 0; i < 6; i++) x[6 + i] = us[(int64_t)i * a.P];
+    }
+    for (int q = 0; q < 2; q++)
+        if (R.g0 + R.n + q < R.hi)
+            a.write_frame(R.g0 + R.n + q, R.p, a.load_out(R.g0 + R.n + q, R.p), x[6 + 3 * q], x[7 + 3 * q], x[8 + 3 * q]);
+    // the factor and the input frame of step i-1 are requested while step i is solved
+    double fc[kFacDoubles], fn[kFacDoubles];
+    typename A::Out rc = a.load_out(R.g0 + R.n - 1, R.p), rn = rc;
+    {
+        const double* f = a.fac + fac_index(a, R.n - 1, lane);
+#pragma unroll
+        for (int k = 0; k < kFacDoubles; k++) fc[k] = f[k * kSmBlock];
+    }
+    for (int i = R.n - 1; i >= 0; i--) {
+        if (i > 0) {
+            const double* f = a.fac + fac_index(a, i - 1, lane);
+#pragma unroll
+            for (int k = 0; k < kFacDoubles; k++) fn[k] = f[k * kSmBlock];
+            rn = a.load_out(R.g0 + i - 1, R.p);
+        }
+        double xa[3];
+#pragma unroll
+        for (int d = 0; d < 3; d++) xa[d] = fc[36 + d];
+#pragma unroll
+        for (int o = 0; o < 12; o++)
+#pragma unroll
+            for (int d = 0; d < 3; d++) xa[d] -= fc[3 * o + d] * x[o];
+        a.write_frame(R.g0 + i, R.p, rc, xa[0], xa[1], xa[2]);
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            x[9 + d] = x[6 + d];
+            x[6 + d] = xa[d];
+        }
+        if (i > 0) {
+#pragma unroll
+            for (int k = 0; k < kFacDoubles; k++) fc[k] = fn[k];
+            rc = rn;
+        }
+    }
+}
+
+// ----------------------------------------------------------------- host side
+struct SmoothPlan {
+    int chunk, n_chunks, n_seps, steps;
+    int64_t n_lanes, n_blocks;
+    int64_t off_fac, off_schur, off_red, off_usol, off_cnt, off_bad, off_fail, bytes;
+};
+
+inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+// chunk = 0: the automatic rule ("Trajectory smoothing": the sweep it comes from).
+// A lane's two sweeps cost about 2·chunk steps, the serial reduce one longer step per separator,
+// T / chunk of them: the minimum lies at a multiple of sqrt(T), 1.25 on the MI355X.
+inline int auto_chunk(int T) {
+    int c = (int)lround(1.25 * sqrt((double)T));
+    return c < kMinChunk ? kMinChunk : c > kMaxChunk ? kMaxChunk : c;
+}
+
+inline SmoothPlan smooth_plan(const char* fn, int T, int P, int chunk) {
+    MVP_REQUIRE(T >= 1, "%s: T=%d < 1", fn, T);
+    MVP_REQUIRE(P >= 1, "%s: P=%d < 1", fn, P);
+    MVP_REQUIRE(chunk == 0 || (chunk >= kMinChunk && chunk <= kMaxChunk), "%s: chunk=%d (0 = automatic, or %d..%d)", fn,
+                chunk, kMinChunk, kMaxChunk);
+    SmoothPlan pl;
+    pl.chunk = chunk == 0 ? auto_chunk(T) : chunk;
+    const int period = pl.chunk + 2;
+    pl.n_chunks = (T + period - 1) / period;
+    pl.n_seps = T > pl.chunk ? (T - pl.chunk - 1) / period + 1 : 0;
+    pl.steps = T < pl.chunk ? T : pl.chunk;
+    pl.n_lanes = (int64_t)P * pl.n_chunks;
+    pl.n_blocks = (pl.n_lanes + kSmBlock - 1) / kSmBlock;
+    MVP_REQUIRE(pl.n_blocks < (1LL << 31), "%s: too many lanes (T=%d, P=%d)", fn, T, P);
+    int64_t b = 0;
+    pl.off_fac = b;
+    b = align256(b + (int64_t)pl.steps * pl.n_blocks * kFacDoubles * kSmBlock * 8);
+    pl.off_schur = b;
+    b = align256(b + pl.n_blocks * kSchurDoubles * kSmBlock * 8);
+    pl.off_red = b;
+    b = align256(b + (int64_t)pl.n_seps * kRedDoubles * P * 8);
+    pl.off_usol = b;
+    b = align256(b + (int64_t)pl.n_seps * 6 * P * 8);
+    pl.off_cnt = b;   // cnt and bad lie together: one memset zeroes both
+    b += (int64_t)P * 4;
+    pl.off_bad = b;
+    b = align256(b + (int64_t)P * 4);
+    pl.off_fail = b;
+    b = align256(b + (int64_t)P * 4);
+    pl.bytes = b;
+    return pl;
+}
+
+}  // namespace

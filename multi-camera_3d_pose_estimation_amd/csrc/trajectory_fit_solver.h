@@ -1,0 +1,111 @@
+// The trajectory fit's side of the partition solver (smooth_solver.h): the per-chain state, the
+// frame source that reads the information-form buffer and writes the trial state, and the
+// workspace plan.  Apart from trajectory_fit.hip's kernels, so that a host program can run the
+// sweeps lane by lane (tools/solver_host_check.cpp) without compiling them.
+#pragma once
+#include "smooth_solver.h"
+
+namespace {
+
+constexpr int kFitTile = 256;   // frames per workgroup of the sum kernel
+constexpr int kFitRows = 4;     // its rows of 64 lanes (lanes along p)
+
+// The per-chain state of a fit, all [P].
+struct FitChain {
+    double* mu;
+    double* f;        // the state's cost
+    double* fseed;
+    int* cur;         // which of the two buffers of x64 holds the state
+    int* done;
+    int* status;      // the status byte
+    int* relin;       // the state moved: linearise again
+    int* rej;         // a pivot of the last solve was not > 0
+};
+
+// The solver's frames.
+struct FitRaw {
+    double h[6], b[3];
+};
+struct FitX {
+    double x[3];
+};
+
+struct FitSolveArgs : SolveCore {
+    const double* H;    // [T][P][6]
+    const double* g;    // [T][P][3], the right-hand side
+    double* x64;        // [2][T][P][3]
+    FitChain ch;
+    using Raw = FitRaw;
+    using Out = FitX;
+    static constexpr bool kInfoForm = true;
+    MVP_SMOOTH_HD double damp(int p) const { return 1.0 + ch.mu[p]; }
+    MVP_SMOOTH_HD bool skip(int p) const { return ch.done[p] != 0; }
+    MVP_SMOOTH_HD FitRaw load_raw(int t, int p) const {
+        const int64_t e = (int64_t)t * P + p;
+        FitRaw f;
+#pragma unroll
+        for (int k = 0; k < 6; k++) f.h[k] = H[6 * e + k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) f.b[k] = g[3 * e + k];
+        return f;
+    }
+    // every frame has a block, if a zero one: nothing is counted
+    MVP_SMOOTH_HD bool frame_weight(const FitRaw& f, double (&W)[6], double (&z)[3]) const {
+#pragma unroll
+        for (int k = 0; k < 6; k++) W[k] = f.h[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) z[k] = f.b[k];
+        return false;
+    }
+    MVP_SMOOTH_HD void finish(int p, int, int bad_pivot) const { ch.rej[p] = bad_pivot; }
+    MVP_SMOOTH_HD bool failed(int) const { return false; }
+    MVP_SMOOTH_HD void write_failed(int, int) const {}
+    MVP_SMOOTH_HD FitX load_out(int t, int p) const {
+        const int64_t e = (int64_t)ch.cur[p] * T * P + (int64_t)t * P + p;
+        FitX f;
+#pragma unroll
+        for (int k = 0; k < 3; k++) f.x[k] = x64[3 * e + k];
+        return f;
+    }
+    // the trial state X + δ, into the chain's other buffer
+    MVP_SMOOTH_HD void write_frame(int t, int p, const FitX& f, double d0, double d1, double d2) const {
+        const int64_t e = (int64_t)(ch.cur[p] ^ 1) * T * P + (int64_t)t * P + p;
+        x64[3 * e + 0] = f.x[0] + d0;
+        x64[3 * e + 1] = f.x[1] + d1;
+        x64[3 * e + 2] = f.x[2] + d2;
+    }
+};
+
+struct FitPlan {
+    SmoothPlan sp;
+    int n_tiles;
+    int64_t sum_blocks;   // the sum kernel's workgroups: frame tiles x tiles of 64 chains
+    int64_t off_chain, off_x, off_H, off_g, off_c2, off_part, bytes;
+};
+
+inline FitPlan fit_plan(const char* fn, int T, int P, int chunk) {
+    FitPlan pl;
+    pl.sp = smooth_plan(fn, T, P, chunk);
+    MVP_REQUIRE((int64_t)T * P < (1LL << 31), "%s: T·P=%lld must be < 2^31", fn, (long long)T * P);
+    const int64_t n = (int64_t)T * P;
+    pl.n_tiles = (T + kFitTile - 1) / kFitTile;
+    pl.sum_blocks = (int64_t)pl.n_tiles * ((P + 63) / 64);
+    MVP_REQUIRE(pl.sum_blocks < (1LL << 31), "%s: too many tiles (T=%d, P=%d)", fn, T, P);
+    int64_t b = pl.sp.bytes;
+    pl.off_chain = b;
+    b = align256(b + (int64_t)P * (3 * 8 + 5 * 4));
+    pl.off_x = b;
+    b = align256(b + 2 * n * 3 * 8);
+    pl.off_H = b;
+    b = align256(b + n * 6 * 8);
+    pl.off_g = b;
+    b = align256(b + n * 3 * 8);
+    pl.off_c2 = b;
+    b = align256(b + n * 2 * 8);
+    pl.off_part = b;
+    b = align256(b + (int64_t)pl.n_tiles * P * 2 * 8);
+    pl.bytes = b;
+    return pl;
+}
+
+}  // namespace

@@ -539,3 +539,97 @@ def bundle_adjust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int]
          float(huber_delta), float(trans_prior_sigma), int(max_iter), float(tol), _ptr(work), nbytes.value,
          _ptr(out_cams), _ptr(out), _ptr(status), _ptr(cov), _ptr(info), _stream(dev))
     return out_cams, out, status, cov, info
+
+
+def trajectory_fit_plan(T: int, P: int, chunk: int = 0):
+    """What trajectory_fit will use for (T, P, chunk) (mvp_trajectory_fit_plan): the chunk length
+    of its time-parallel solve, the chunks per chain and the workspace bytes."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_trajectory_fit_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
+         ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
+def _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask):
+    """Shared front of the two trajectory-fit calls: checks and the packed arguments."""
+    if weights not in REFINE_WEIGHTS:
+        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
+    V, lead, _, ci = _tri_args(kpts, cams, cam_idx)
+    if len(lead) != 2:
+        raise ValueError(f"kpts must be (T, P, 3, V), got {tuple(kpts.shape)}")
+    T, P = int(lead[0]), int(lead[1])
+    nv = len(ci)
+    _require(xyz, torch.float32, "xyz")
+    if tuple(xyz.shape) != (T, P, 3):
+        raise ValueError(f"xyz must be {(T, P, 3)}, got {tuple(xyz.shape)}")
+    if weights == "heatmap":
+        if gauss is None:
+            raise ValueError('weights="heatmap" needs gauss, the (T, V, P, 6) float64 heatmap Gaussians')
+        _require(gauss, torch.float64, "gauss")
+        if tuple(gauss.shape) != (T, V, P, 6):
+            raise ValueError(f"gauss must be {(T, V, P, 6)}, got {tuple(gauss.shape)}")
+    bits = None
+    if mask is not None:
+        _require(mask, torch.bool, "mask")
+        if tuple(mask.shape) != (T, P, nv):
+            raise ValueError(f"mask must be {(T, P, nv)}, got {tuple(mask.shape)}")
+        bits = _pack_view_bits(mask)
+    return V, T, P, ci, nv, bits
+
+
+def trajectory_fit_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz: torch.Tensor, *,
+                          weights: str = "conf", gauss: torch.Tensor | None = None,
+                          mask: torch.Tensor | None = None, min_conf: float = 0.0, cov_floor: float = 1.0,
+                          huber_delta: float = 0.0):
+    """One linearisation of the trajectory fit's data term (mvp_trajectory_fit_system; stated in
+    include/mvpose.h) at the float32 trajectory xyz (T, P, 3).
+
+    kpts (T, P, 3, V), cams, cam_idx, weights, gauss (T, V, P, 6), mask (T, P, NV) bool, min_conf,
+    cov_floor as for triangulate_refine; huber_delta as for bundle_adjust.  Returns (H (T, P, 6)
+    float64: Σ Jᵀ W̃ J per frame as (xx, xy, xz, yy, yz, zz); g (T, P, 3) float64: Σ Jᵀ W̃ r;
+    nviews (T, P) uint8: used views; cost (P, 2) float64: Σ rho and ½ Σ |second difference|² per
+    chain), all on the GPU."""
+    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    dev = kpts.device
+    H = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
+    g = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    call("mvp_trajectory_fit_system", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
+         _ptr(H), _ptr(g), _ptr(nviews), _ptr(cost), _stream(dev))
+    return H, g, nviews, cost
+
+
+def trajectory_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz0: torch.Tensor, *,
+                   weights: str = "conf", gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None,
+                   min_conf: float = 0.0, cov_floor: float = 1.0, huber_delta: float = 0.0,
+                   lambda_smooth: float = 1.0, max_iter: int = 30, tol: float = 1e-6, chunk: int = 0):
+    """Trajectories fitted to the 2D keypoints (mvp_trajectory_fit; the problem and the solver are
+    stated in include/mvpose.h): per chain p the minimiser of the used views' reprojection cost plus
+    ½ lambda_smooth Σ |X_t − 2 X_{t−1} + X_{t−2}|², by Levenberg-Marquardt from the seed xyz0
+    (T, P, 3) float32.  A frame seen by one view still pins two of its three coordinates; a frame
+    seen by none is carried by the prior.  Arguments as for trajectory_fit_system; at most
+    max_iter trials (0..63), converged at an accepted cost decrease <= tol·cost; chunk as for
+    trajectory_smooth.  Stream-ordered, no host synchronisation.
+
+    Returns (xyz (T, P, 3) float32; resid (T, P) float32: Σ over the used views of the whitened
+    squared residual at the result, NaN without a used view; nviews (T, P) uint8; cost (P, 2)
+    float64: the cost at the seed and at the result; status (P,) uint8: bits 0-5 the trials, 0x40
+    not converged, 0x80 invalid chain (returned as its seed; NaN resid and cost)), all on the GPU."""
+    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask)
+    _, _, nbytes = trajectory_fit_plan(T, P, chunk)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((T, P, 3), dtype=torch.float32, device=dev)
+    resid = torch.empty((T, P), dtype=torch.float32, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    status = torch.empty((P,), dtype=torch.uint8, device=dev)
+    call("mvp_trajectory_fit", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
+         float(lambda_smooth), int(max_iter), float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out),
+         _ptr(resid), _ptr(nviews), _ptr(cost), _ptr(status), _stream(dev))
+    return out, resid, nviews, cost, status

@@ -229,7 +229,8 @@ class MultiViewPipeline:
         return out
 
     @staticmethod
-    def people_trajectories(out: dict, min_len: int = 1, max_people: int | None = None, **track_kw) -> dict:
+    def people_trajectories(out: dict, min_len: int = 1, max_people: int | None = None, with_2d: bool = False,
+                            **track_kw) -> dict:
         """One trajectory per person from a process_people result, or from the concatenation along
         time of several chunks' results (group numbers are per frame; this is what gives a person
         one number through the recording).  people.track_people on kpts_3d (track_kw: max_gap,
@@ -242,13 +243,19 @@ class MultiViewPipeline:
         tri_refine_status_person (T, Np, 17) uint8 (0 where absent; the NaN points mark those
         frames).  refine.smooth_trajectory takes person p as kpts_3d_person[:, p],
         cov=kpts_3d_cov_person[:, p], status=tri_refine_status_person[:, p], and fills the frames
-        the person was not seen in."""
+        the person was not seen in.
+        with_2d=True also gathers what refine.fit_trajectory reads: kpts_2d_person
+        (T, Np, 17, 3, V), heatmaps_2d_person (T, Np, V, 17, 6) and tri_inliers_person
+        (T, Np, 17, NV) bool (its mask), NaN / False where the person is absent."""
         from . import people
         xyz = out["kpts_3d"]
         if xyz.dim() != 4 or xyz.shape[3] != 3:
             raise ValueError(f"out['kpts_3d'] must be (T, G, J, 3) as process_people returns it, got {tuple(xyz.shape)}")
         track, _ = people.track_people(xyz.contiguous(), **track_kw)
-        arrays = {k: out[k] for k in ("kpts_3d", "kpts_3d_cov", "tri_refine_status") if k in out}
+        names = ("kpts_3d", "kpts_3d_cov", "tri_refine_status")
+        if with_2d:
+            names += ("kpts_2d", "heatmaps_2d", "tri_inliers")
+        arrays = {k: out[k] for k in names if k in out}
         got, present, chosen = people.person_trajectories(track, arrays, min_len=min_len, max_people=max_people)
         res = {k + "_person": v for k, v in got.items()}
         res["person_present"] = present

@@ -13,6 +13,8 @@ Host mirror of the reference's refinement API (pose_refinement.py):
 * ``project_points_torch`` (:94-179) and ``linear_interpolation`` (:15-84) on the GPU.
 * ``smooth_trajectory`` (no reference counterpart): covariance-weighted smoothing of a whole
   recording with gap filling, a direct solve on the GPU (mvp_trajectory_smooth).
+* ``fit_trajectory`` (no reference counterpart): trajectories fitted to the 2D keypoints plus the
+  same smoothness prior, so that frames seen by one camera count (mvp_trajectory_fit).
 
 * Extrinsic learning from samples (``sgd_optimize(extrinsic_optimization_IDs=[id],
   optimize_trajectory=False, GT_camera_IDs=[a, b])``, :684-706, :800-831, :915-943):
@@ -302,6 +304,83 @@ def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1
         res = out.cpu().numpy()
         info = {"resid": resid.cpu().numpy(), "observed": observed.cpu().numpy(), "status": st_out.cpu().numpy()}
     return (res, info) if return_info else res
+
+
+def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="conf", gauss=None, mask=None,
+                   lambda_smooth=1.0, huber_px=0.0, min_conf=0.0, cov_floor=1.0, max_iter=30, tol=1e-6, chunk=0,
+                   return_info=False, device=None):
+    """Trajectories fitted to the 2D keypoints, so that a frame seen by a single camera still counts
+    (mvp_trajectory_fit, stated in include/mvpose.h; no reference counterpart: the reference's
+    sgd_optimize scores the same pixels, in f32 with Adam, with no mask, no robust loss and no
+    weights of a view's own).  Per joint the minimiser of the used views' reprojection cost plus
+    ½ lambda_smooth Σ |X_t − 2 X_{t−1} + X_{t−2}|², by Levenberg-Marquardt from `seed`.
+
+    kpts_2d (T, J, 3, V), or (T, Np, J, 3, V) for Np people (folded to Np·J independent chains);
+    camera_params as get_pose_3D takes them ({index: [K, R, T, dist]}); seed (T, J, 3) or
+    (T, Np, J, 3), typically smooth_trajectory's gap-filled output: it has to be finite in every
+    frame and in front of every camera that sees the joint, or the joint is returned as it came.
+    camera_indices: the views used (default: all of camera_params, in order).  weights "unit",
+    "conf" or "heatmap" as for triangulate_refine, the last with gauss = heatmaps_2d (T, V, J, 6),
+    or (T, Np, V, J, 6) as process_people returns it per group.  mask (T, [Np,] J, NV) bool: the
+    views a point may use, e.g. tri_inliers; a point with no view set (one that did not
+    triangulate) may use every view.  Such a point's views were never tested against each other, so
+    set huber_px (the Huber threshold on the whitened residual, in pixels for unit weights) when the
+    2D detections can be wrong; 0 = plain least squares.
+
+    lambda_smooth weighs world units² against the data term: with unit weights, (σ_px / σ_a)² for
+    keypoint noise σ_px and a per-frame second difference of σ_a.  Over a long stretch seen by one
+    camera only, the depth along that camera's rays is held by the prior alone; with a weak prior
+    it wanders (the numpy restatement on the synthetic two-camera rig, 40 single-view frames: at
+    0.25 the fit is 62-89 cm off where smooth_trajectory's blind interpolation is 16-19 cm off; at
+    4 the two are level, 7-15 cm against 9-12 cm): such recordings need a stiffer prior.
+
+    Returns float32 of seed's shape (numpy in, numpy out; tensors stay tensors); return_info=True
+    returns (points, {"resid" (T, [Np,] J) float32: Σ over the used views of the whitened squared
+    residual, NaN without a view; "nviews" uint8; "cost" ([Np,] J, 2) float64: at the seed and at the
+    result; "status" ([Np,] J) uint8: bits 0-5 the trials, 0x40 not converged, 0x80 returned as it
+    came})."""
+    was_tensor = isinstance(seed, torch.Tensor)
+    k = kpts_2d if isinstance(kpts_2d, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(kpts_2d)))
+    if k.dim() not in (4, 5) or k.shape[-2] != 3:
+        raise ValueError(f"kpts_2d must be (T, J, 3, V) or (T, Np, J, 3, V), got {tuple(k.shape)}")
+    home = seed.device if was_tensor else torch.device("cpu")
+    dev = _device(device if device is not None else (k.device if k.device.type == "cuda" else "cuda"))
+    lead = tuple(k.shape[:-2])
+    T, P, V = int(lead[0]), int(np.prod(lead[1:])), int(k.shape[-1])
+    k = k.to(device=dev, dtype=torch.float32).reshape(T, P, 3, V).contiguous()
+    x0 = torch.as_tensor(seed)
+    if tuple(x0.shape) != lead + (3,):
+        raise ValueError(f"seed must be {lead + (3,)}, got {tuple(x0.shape)}")
+    x0 = x0.to(device=dev, dtype=torch.float32).reshape(T, P, 3).contiguous()
+    idx = sorted(camera_params) if camera_indices is None else [int(c) for c in camera_indices]
+    cams = torch.as_tensor(ops.pack_cameras(camera_params), device=dev)
+    g = None
+    if weights == "heatmap":
+        if gauss is None:
+            raise ValueError('weights="heatmap" needs gauss, the heatmap Gaussians')
+        g = torch.as_tensor(gauss).to(device=dev, dtype=torch.float64)
+        if len(lead) == 3:
+            if tuple(g.shape) != (T, lead[1], V, lead[2], 6):
+                raise ValueError(f"gauss must be {(T, lead[1], V, lead[2], 6)}, got {tuple(g.shape)}")
+            g = g.permute(0, 2, 1, 3, 4)
+        g = g.reshape(T, V, P, 6).contiguous()
+    m = None
+    if mask is not None:
+        m = torch.as_tensor(mask).to(device=dev, dtype=torch.bool)
+        if tuple(m.shape) != lead + (len(idx),):
+            raise ValueError(f"mask must be {lead + (len(idx),)}, got {tuple(m.shape)}")
+        m = (m | ~m.any(-1, keepdim=True)).reshape(T, P, len(idx)).contiguous()
+    out, resid, nviews, cost, status = ops.trajectory_fit(
+        k, cams, idx, x0, weights=weights, gauss=g, mask=m, min_conf=min_conf, cov_floor=cov_floor,
+        huber_delta=huber_px, lambda_smooth=lambda_smooth, max_iter=max_iter, tol=tol, chunk=chunk)
+    info = {"resid": resid.reshape(lead), "nviews": nviews.reshape(lead), "cost": cost.reshape(lead[1:] + (2,)),
+            "status": status.reshape(lead[1:])}
+    out = out.reshape(lead + (3,))
+    if was_tensor:
+        out, info = out.to(home), {n: v.to(home) for n, v in info.items()}
+    else:
+        out, info = out.cpu().numpy(), {n: v.cpu().numpy() for n, v in info.items()}
+    return (out, info) if return_info else out
 
 
 EXT_SUMS = 14

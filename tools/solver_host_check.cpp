@@ -1,0 +1,140 @@
+// Drives the information-form sweep of the trajectory fit (eliminate, reduce, backsub of
+// csrc/smooth_solver.h over the frame source of csrc/trajectory_fit_solver.h) on the HOST, lane by lane, and
+// compares the trial state with a dense Cholesky solve of the same damped system.  The per-lane
+// functions compile for the host, so this is where a sanitizer can watch their indexing:
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Iinclude -Imulti-camera_3d_pose_estimation_amd/csrc \
+//         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//         tools/solver_host_check.cpp multi-camera_3d_pose_estimation_amd/csrc/abi.cpp \
+//         -o /tmp/solver_host_check && /tmp/solver_host_check
+//
+// No device call is made; the program needs no GPU.
+#include "../multi-camera_3d_pose_estimation_amd/csrc/trajectory_fit_solver.h"
+
+#include <cstdio>
+#include <random>
+#include <vector>
+
+namespace {
+
+// Dense A (n x n, row-major, SPD) x = b by Cholesky; false on a pivot that is not > 0.
+bool dense_solve(std::vector<double> A, std::vector<double> b, int n, std::vector<double>& x) {
+    for (int j = 0; j < n; j++) {
+        double d = A[j * n + j];
+        for (int k = 0; k < j; k++) d -= A[j * n + k] * A[j * n + k];
+        if (!(d > 0)) return false;
+        const double l = std::sqrt(d);
+        A[j * n + j] = l;
+        for (int i = j + 1; i < n; i++) {
+            double v = A[i * n + j];
+            for (int k = 0; k < j; k++) v -= A[i * n + k] * A[j * n + k];
+            A[i * n + j] = v / l;
+        }
+    }
+    for (int i = 0; i < n; i++) {
+        double v = b[i];
+        for (int k = 0; k < i; k++) v -= A[i * n + k] * b[k];
+        b[i] = v / A[i * n + i];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double v = b[i];
+        for (int k = i + 1; k < n; k++) v -= A[k * n + i] * b[k];
+        b[i] = v / A[i * n + i];
+    }
+    x = b;
+    return true;
+}
+
+double check(int T, int P, int chunk, double lambda, unsigned seed) {
+    const FitPlan pl = fit_plan("solver_host_check", T, P, chunk);
+    std::vector<char> ws((size_t)pl.bytes);   // exactly the plan's bytes: an index past them is an error
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> uni(-1.0, 1.0);
+    const int64_t n = (int64_t)T * P;
+    std::vector<double> H(6 * n), g(3 * n), x64(2 * 3 * n), mu(P);
+    std::vector<int> cur(P), done(P, 0), rej(P, 0);
+    for (int p = 0; p < P; p++) mu[p] = 1e-3 * (p + 1), cur[p] = p & 1;
+    for (int64_t e = 0; e < n; e++) {
+        // rank 3, rank 2 (one view) and empty frames in turn; the first two frames are full
+        const int t = (int)(e / P), kind = t < 2 ? 0 : (int)((e + t) % 3);
+        double J[3][3];
+        for (auto& row : J)
+            for (double& v : row) v = uni(rng);
+        for (int r = kind == 0 ? 3 : kind == 1 ? 2 : 0; r < 3; r++) J[r][0] = J[r][1] = J[r][2] = 0.0;
+        const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+        for (int k = 0; k < 6; k++) {
+            double s = 0.0;
+            for (int r = 0; r < 3; r++) s += J[r][ij[k][0]] * J[r][ij[k][1]];
+            H[6 * e + k] = s;
+        }
+        for (int k = 0; k < 3; k++) g[3 * e + k] = uni(rng);
+        for (int b = 0; b < 2; b++)
+            for (int k = 0; k < 3; k++) x64[3 * (b * n + e) + k] = 100.0 * uni(rng);
+    }
+    FitSolveArgs sa{};
+    sa.T = T, sa.P = P, sa.chunk = pl.sp.chunk, sa.n_chunks = pl.sp.n_chunks, sa.n_seps = pl.sp.n_seps;
+    sa.n_lanes = pl.sp.n_lanes, sa.n_blocks = pl.sp.n_blocks, sa.lambda = lambda;
+    sa.fac = reinterpret_cast<double*>(ws.data() + pl.sp.off_fac);
+    sa.schur = reinterpret_cast<double*>(ws.data() + pl.sp.off_schur);
+    sa.red = reinterpret_cast<double*>(ws.data() + pl.sp.off_red);
+    sa.usol = reinterpret_cast<double*>(ws.data() + pl.sp.off_usol);
+    sa.cnt = reinterpret_cast<int*>(ws.data() + pl.sp.off_cnt);
+    sa.bad = reinterpret_cast<int*>(ws.data() + pl.sp.off_bad);
+    for (int p = 0; p < P; p++) sa.cnt[p] = sa.bad[p] = 0;
+    sa.H = H.data(), sa.g = g.data(), sa.x64 = x64.data();
+    sa.ch.mu = mu.data(), sa.ch.cur = cur.data(), sa.ch.done = done.data(), sa.ch.rej = rej.data();
+    const std::vector<double> before = x64;
+    for (int64_t lane = 0; lane < sa.n_lanes; lane++) eliminate_lane(sa, lane);
+    for (int p = 0; p < P; p++) reduce_chain(sa, p);
+    for (int64_t lane = 0; lane < sa.n_lanes; lane++) backsub_lane(sa, lane);
+    double worst = 0.0;
+    for (int p = 0; p < P; p++) {
+        const int m = 3 * T;
+        std::vector<double> A((size_t)m * m, 0.0), b(m), x;
+        for (int s = 2; s < T; s++) {
+            const double v[3] = {1.0, -2.0, 1.0};
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++)
+                    for (int d = 0; d < 3; d++) A[(3 * (s - 2 + i) + d) * m + 3 * (s - 2 + j) + d] += lambda * v[i] * v[j];
+        }
+        for (int t = 0; t < T; t++) {
+            const double* h = &H[6 * ((int64_t)t * P + p)];
+            const double full[3][3] = {{h[0], h[1], h[2]}, {h[1], h[3], h[4]}, {h[2], h[4], h[5]}};
+            for (int i = 0; i < 3; i++) {
+                for (int j = 0; j < 3; j++) A[(3 * t + i) * m + 3 * t + j] += full[i][j];
+                b[3 * t + i] = g[3 * ((int64_t)t * P + p) + i];
+            }
+        }
+        for (int i = 0; i < m; i++) A[i * m + i] *= 1.0 + mu[p];
+        if (!dense_solve(A, b, m, x) || rej[p]) {
+            std::printf("T=%d P=%d chunk=%d chain %d: pivot failure (dense %d, sweep %d)\n", T, P, chunk, p, 1, rej[p]);
+            return 1.0;
+        }
+        for (int t = 0; t < T; t++)
+            for (int k = 0; k < 3; k++) {
+                const int64_t e = (int64_t)t * P + p;
+                const double want = before[3 * (cur[p] * n + e) + k] + x[3 * t + k];
+                const double got = x64[3 * ((cur[p] ^ 1) * n + e) + k];
+                const double keep = x64[3 * (cur[p] * n + e) + k] - before[3 * (cur[p] * n + e) + k];
+                worst = std::fmax(worst, std::fabs(got - want) / (1.0 + std::fabs(x[3 * t + k])));
+                worst = std::fmax(worst, std::fabs(keep));   // the state itself is not written
+            }
+    }
+    return worst;
+}
+
+}  // namespace
+
+int main() {
+    const int Ts[] = {1, 2, 3, 4, 5, 6, 7, 8, 11, 12, 13, 40, 200};
+    double worst = 0.0;
+    for (int T : Ts)
+        for (int chunk : {4, 0})
+            for (int P : {1, 3, 65}) {
+                const double w = check(T, P, chunk, 0.7, 17u * T + P);
+                std::printf("T=%d P=%d chunk=%d: largest relative difference to the dense solve %.3g\n", T, P, chunk, w);
+                worst = std::fmax(worst, w);
+            }
+    std::printf("worst %.3g\n", worst);
+    return worst < 1e-9 ? 0 : 1;
+}
