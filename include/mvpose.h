@@ -341,6 +341,14 @@ int mvp_graph_destroy(void* handle);
  * tools/fwd_breakdown.py pairs the records with a kernel trace. */
 int mvp_graph_plan(void* handle, int batch, int64_t* rec_out, int max_records, int* n_records,
                    int64_t* covered_macs_out);
+/* Diagnostics: the kernel family each of those launches runs, one id per record of
+ * mvp_graph_plan in the same order.  The graph chooses a launch's kernel when it is created,
+ * from the op's shape, its route and the MVPOSE_* switches as the environment had them then;
+ * where the choice depends on the batch (the crop-streaming kernels, from one crop per CU) a
+ * smaller last micro-batch may show another kernel than the full ones.  mvp_graph_kernel_name:
+ * the kernel function's base name as a kernel trace shows it ("" for an unknown id). */
+int mvp_graph_kernels(void* handle, int batch, int* kernels_out, int max_records, int* n_records);
+const char* mvp_graph_kernel_name(int kernel);
 
 /* ---------------------------------------------------------------------------
  * Person detector: RTMDet-m (the reference's `detectors.coco_base`,

@@ -592,8 +592,6 @@ __global__ __launch_bounds__(512, 1) void bneck_kernel(BNParams p) {
 }  // namespace
 
 bool bneck_supported(int H, int W, int C, int M) {
-    const char* e = getenv("MVPOSE_NO_BNECK");  // tests / A/B: the tconv + Bottleneck-join path
-    if (e && e[0] == '1') return false;
     using BN = BNT<false>;
     return H == BN::H && W == BN::W && (C == BNT<false>::C || C == BNT<true>::C) && M == BN::M;
 }

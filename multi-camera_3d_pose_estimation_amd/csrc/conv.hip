@@ -529,9 +529,9 @@ void launch_tile2(const ConvParams& p, hipStream_t s) {
         launch_tile<KS, S, TH, TW, NB, 4>(p, s);
 }
 
-// Tile shape per output plane.
+// Tile shape per output plane.  s2_tile: ConvLaunch::s2_tile (3x3/s2 tuning experiments only).
 template <int KS, int S>
-void launch_plane(const ConvParams& p, hipStream_t s) {
+void launch_plane(const ConvParams& p, int s2_tile, hipStream_t s) {
     if constexpr (S == 1) {
         if (p.Wo == 48 && p.Ho % 8 == 0)
             launch_tile2<KS, S, 4, 48, 1, 8, 48, 1>(p, s);
@@ -544,8 +544,7 @@ void launch_plane(const ConvParams& p, hipStream_t s) {
         else
             launch_tile<KS, S, 4, 16, 1, 4>(p, s);  // generic masked tiling
     } else {
-        const char* e = getenv("MVPOSE_S2_TILE");  // tuning experiments only
-        const int v = e ? atoi(e) : 0;  // 7: the pre-sweep 4-wave default
+        const int v = s2_tile;  // 7: the pre-sweep 4-wave default
         if (v == 1 && p.Wo % 8 == 0 && p.Ho % 16 == 0) return launch_tile<KS, S, 16, 8, 1, 4>(p, s);
         if (v == 2 && p.Wo % 8 == 0 && p.Ho % 8 == 0) return launch_tile<KS, S, 8, 8, 2, 4>(p, s);
         if (v == 3 && p.Wo % 16 == 0 && p.Ho % 8 == 0) return launch_tile<KS, S, 8, 16, 1, 4>(p, s);
@@ -765,9 +764,8 @@ __global__ __launch_bounds__(256) void fuse_sum_n_kernel(FuseParams p) {
 
 const uint16_t* conv_zero_region() { return zero_page(); }
 
-int conv_cout_pad(int cout) { return cout <= 32 ? 32 : ((cout + 63) / 64) * 64; }
-
-void launch_conv_impl(const ConvLaunch& c, hipStream_t s, bool generic_only) {
+void launch_conv_generic(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(!c.x2, "conv: the generic kernel takes one input");
     MVP_REQUIRE(c.Cin % 32 == 0, "conv: Cin=%d must be a multiple of 32", c.Cin);
     MVP_REQUIRE(c.ks == 1 || c.ks == 3, "conv: ks=%d", c.ks);
     MVP_REQUIRE(c.stride == 1 || c.stride == 2, "conv: stride=%d", c.stride);
@@ -794,38 +792,16 @@ void launch_conv_impl(const ConvLaunch& c, hipStream_t s, bool generic_only) {
     p.relu = c.relu;
     p.out_f32 = c.out_f32_nchw;
     if (c.N == 0) return;
-    if (generic_only) {
-        MVP_REQUIRE(!c.x2 && !c.out_f32_nchw, "conv: the generic path takes one bf16 input and output");
-        goto generic;
-    }
-    if (c.x2) {  // graph cat-fusion: only the direct 1x1 kernel reads two inputs
-        MVP_REQUIRE(c.ks == 1 && launch_conv1x1_direct(c, s), "conv: dual-input conv needs the 1x1 kernel");
-        MVP_HIP(hipGetLastError());
-        return;
-    }
-    if (launch_head1x1(c, s) || launch_conv1x1_direct(c, s) || launch_tconv(c, s) ||
-        launch_s2conv(c, s)) {
-        MVP_HIP(hipGetLastError());
-        return;
-    }
-generic:
     if (c.ks == 3 && c.stride == 1)
-        launch_plane<3, 1>(p, s);
+        launch_plane<3, 1>(p, c.s2_tile, s);
     else if (c.ks == 3 && c.stride == 2)
-        launch_plane<3, 2>(p, s);
+        launch_plane<3, 2>(p, c.s2_tile, s);
     else if (c.ks == 1 && c.stride == 1)
-        launch_plane<1, 1>(p, s);
+        launch_plane<1, 1>(p, c.s2_tile, s);
     else
         fail(MVP_ERR_ARG, "conv: unsupported ks=%d stride=%d", c.ks, c.stride);
     MVP_HIP(hipGetLastError());
 }
-
-void launch_conv(const ConvLaunch& c, hipStream_t s) {
-    MVP_REQUIRE(!c.x_stride && !c.y_stride && !c.r_stride && c.relu != 2, "conv: views / SiLU need launch_conv_generic");
-    launch_conv_impl(c, s, false);
-}
-
-void launch_conv_generic(const ConvLaunch& c, hipStream_t s) { launch_conv_impl(c, s, true); }
 
 void launch_stem(const uint16_t* x, const float* w, const float* bias, uint16_t* y, int N, int H, int W,
                  hipStream_t s) {

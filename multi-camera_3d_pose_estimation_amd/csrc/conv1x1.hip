@@ -524,21 +524,35 @@ void launch_1x1(const P1x1& p, int cout_pad, hipStream_t s) {
 }
 
 template <int BM>
-bool dispatch_k(const P1x1& p, int kch, int cout_pad, hipStream_t s) {
+void dispatch_k(const P1x1& p, int kch, int cout_pad, hipStream_t s) {
     switch (kch) {
-        case 1: launch_1x1<BM, 1>(p, cout_pad, s); return true;
-        case 2: launch_1x1<BM, 2>(p, cout_pad, s); return true;
-        case 4: launch_1x1<BM, 4>(p, cout_pad, s); return true;
-        case 8: launch_1x1<BM, 8>(p, cout_pad, s); return true;
-        default: return false;
+        case 1: return launch_1x1<BM, 1>(p, cout_pad, s);
+        case 2: return launch_1x1<BM, 2>(p, cout_pad, s);
+        case 4: return launch_1x1<BM, 4>(p, cout_pad, s);
+        case 8: return launch_1x1<BM, 8>(p, cout_pad, s);
+        default: fail(MVP_ERR_ARG, "conv1x1: Cin %d", kch * 32);
     }
+}
+
+// One Bottleneck-join kernel (with or without its second GEMM) on a persistent grid, a wave
+// per 16-pixel unit; its LDS attribute and occupancy are asked on first use.
+template <auto KERN>
+void launch_pair_kernel(const PPair& p, int threads, int lds, hipStream_t s) {
+    static int per_cu = 0;
+    if (per_cu == 0) {
+        MVP_HIP(hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERN, threads, lds));
+        if (per_cu < 1) per_cu = 1;
+    }
+    const long units = (p.n_pix + 15) / 16, waves = threads / 64;
+    const long grid = std::min<long>((long)cu_count() * per_cu, (units + waves - 1) / waves);
+    hipLaunchKernelGGL(KERN, dim3((unsigned)grid), dim3(threads), lds, s, p);
+    MVP_HIP(hipGetLastError());
 }
 
 }  // namespace
 
 bool conv1x1_pair_supported(int cin_total, int cmid, int cout2) {
-    const char* e = getenv("MVPOSE_NO_PAIRFUSE");  // diagnostics/tests: keep the two launches
-    if (e && e[0] == '1') return false;
     return (cin_total == 64 || cin_total == 128) && cmid == 256 && cout2 == 64;
 }
 
@@ -550,81 +564,50 @@ void launch_conv1x1_pair(const PairLaunch& c, hipStream_t s) {
     if (c.n_pix == 0) return;
     PPair p{c.x, c.x2, c.c1, c.x2 ? c.c2 : 0, c.c1 / 32, c.w1, c.b1, c.res, c.y, c.w2, c.b2, c.y2,
             conv_zero_region(), c.n_pix};
-    const long units = (c.n_pix + 15) / 16;
-    auto go = [&](auto kern, int kch) {
-        const int kPairThreads = kch == 2 ? pair_threads<2>() : pair_threads<4>();
-        const int lds = (kch * 4 * 256 + 8 * 4 * 64) * 16 + (kPairThreads / 64) * 4096;
-        MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        int pc = 0;
-        MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, kPairThreads, lds));
-        if (pc < 1) pc = 1;
-        const long grid = std::min<long>((long)cu_count() * pc, (units + kPairThreads / 64 - 1) / (kPairThreads / 64));
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPairThreads), lds, s, p);
-    };
+    auto lds = [](int kch, int threads) { return (kch * 4 * 256 + 8 * 4 * 64) * 16 + (threads / 64) * 4096; };
     // look-ahead depth (units in flight per wave) as measured best per join: 64-ch 1 (1,496 vs
     // 1,575 us per join graph with 2), the cat-fused 128-ch join 3
     MVP_REQUIRE(c.res || c.x2, "conv1x1_pair: a join without residual must be cat-fused");
     if (cin == 64) {
         MVP_REQUIRE(c.res != nullptr, "conv1x1_pair: 64-ch join needs its residual");
-        go(conv1x1_pair_kernel<2, true, 1>, 2);
+        launch_pair_kernel<conv1x1_pair_kernel<2, true, 1>>(p, pair_threads<2>(), lds(2, pair_threads<2>()), s);
     } else if (c.res) {
-        go(conv1x1_pair_kernel<4, true, 1>, 4);
+        launch_pair_kernel<conv1x1_pair_kernel<4, true, 1>>(p, pair_threads<4>(), lds(4, pair_threads<4>()), s);
     } else {
-        go(conv1x1_pair_kernel<4, false, 3>, 4);
+        launch_pair_kernel<conv1x1_pair_kernel<4, false, 3>>(p, pair_threads<4>(), lds(4, pair_threads<4>()), s);
     }
-    MVP_HIP(hipGetLastError());
 }
 
 // A 1x1 conv 64 -> 256 (or the cat-fused 64 + 64 -> 256) with ReLU, + optional 256-ch
 // residual, on the Bottleneck-join kernel without its second GEMM: one wave owns all 256
 // couts of 16 pixels (input read once instead of once per 128-cout column block) and its
 // residual loads / output stores go through LDS as whole 256-B runs.
-bool launch_conv1x1_wide(const ConvLaunch& c, hipStream_t s) {
+void launch_conv1x1_wide(const ConvLaunch& c, hipStream_t s) {
     const int cin = c.Cin;
-    if (c.ks != 1 || c.stride != 1 || c.out_f32_nchw || c.Cout != 256 || !c.relu) return false;
-    if (!(cin == 64 || (cin == 128 && c.x2 && c.c1 == 64))) return false;
-    if (cin == 64 && !c.res) return false;
+    MVP_REQUIRE(c.ks == 1 && c.stride == 1 && !c.out_f32_nchw && c.Cout == 256 && c.relu &&
+                    ((cin == 64 && c.res) || (cin == 128 && c.x2 && c.c1 == 64)),
+                "conv1x1_wide: unsupported conv %d -> %d", cin, c.Cout);
     const long n_pix = (long)c.N * c.H * c.W;
-    if (n_pix == 0) return true;
+    if (n_pix == 0) return;
     PPair p{c.x, c.x2, 64, cin == 128 ? 64 : 0, 2, c.w, c.bias, c.res, c.y, nullptr, nullptr,
             nullptr, conv_zero_region(), n_pix};
-    const long units = (n_pix + 15) / 16;
-    auto go = [&](auto kern, int kch) {
-        const int lds = kch * 4 * 256 * 16 + 8 * 4096;
-        MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        int pc = 0;
-        MVP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&pc, kern, 512, lds));
-        if (pc < 1) pc = 1;
-        const long grid = std::min<long>((long)cu_count() * pc, (units + 7) / 8);
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, p);
-    };
-    if (cin == 64) go(conv1x1_pair_kernel<2, true, 1, false>, 2);
-    else if (c.res) go(conv1x1_pair_kernel<4, true, 1, false>, 4);
-    else go(conv1x1_pair_kernel<4, false, 1, false>, 4);
-    MVP_HIP(hipGetLastError());
-    return true;
+    auto lds = [](int kch) { return kch * 4 * 256 * 16 + 8 * 4096; };
+    if (cin == 64) launch_pair_kernel<conv1x1_pair_kernel<2, true, 1, false>>(p, 512, lds(2), s);
+    else if (c.res) launch_pair_kernel<conv1x1_pair_kernel<4, true, 1, false>>(p, 512, lds(4), s);
+    else launch_pair_kernel<conv1x1_pair_kernel<4, false, 1, false>>(p, 512, lds(4), s);
 }
 
-bool launch_head1x1(const ConvLaunch& c, hipStream_t s) {
-    if (c.ks != 1 || c.stride != 1 || !c.out_f32_nchw || c.Cin != 32 || c.Cout != 17 || c.res || c.relu || c.x2)
-        return false;
-    const char* e = getenv("MVPOSE_NO_HEAD1X1");  // diagnostics/tests: generic conv kernel
-    if (e && e[0] == '1') return false;
+void launch_head1x1(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(c.ks == 1 && c.stride == 1 && c.out_f32_nchw && c.Cin == 32 && c.Cout == 17 && !c.res && !c.relu && !c.x2,
+                "head1x1: unsupported conv %d -> %d", c.Cin, c.Cout);
     const long n_pix = (long)c.N * c.H * c.W;
-    if (n_pix == 0) return true;
+    if (n_pix == 0) return;
     hipLaunchKernelGGL(head1x1_kernel<17>, dim3((unsigned)((n_pix + 255) / 256)), dim3(256), 0, s, c.x, c.w, c.bias,
                        c.yf, n_pix, c.H * c.W);
     MVP_HIP(hipGetLastError());
-    return true;
 }
 
-bool head_fuse_supported(int cin, int cout, int n_in) {
-    const char* e = getenv("MVPOSE_NO_HEADFUSE");  // diagnostics/tests: fuse_sum + head1x1
-    if (e && e[0] == '1') return false;
-    const char* e2 = getenv("MVPOSE_NO_HEAD1X1");
-    if (e2 && e2[0] == '1') return false;
-    return cin == 32 && cout == 17 && n_in >= 1 && n_in <= 4;
-}
+bool head_fuse_supported(int cin, int cout, int n_in) { return cin == 32 && cout == 17 && n_in >= 1 && n_in <= 4; }
 
 void launch_head_fuse(const uint16_t* const* in, const int* up, int n_in, int relu, const uint16_t* w,
                       const float* bias, float* y, int N, int H, int W, hipStream_t s) {
@@ -650,11 +633,10 @@ void launch_head_fuse(const uint16_t* const* in, const int* up, int n_in, int re
     MVP_HIP(hipGetLastError());
 }
 
-bool launch_conv1x1_direct(const ConvLaunch& c, hipStream_t s) {
-    if (c.ks != 1 || c.stride != 1 || c.out_f32_nchw || c.Cin % 32 != 0) return false;
-    if (launch_conv1x1_wide(c, s)) return true;
+void launch_conv1x1_direct(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(c.ks == 1 && c.stride == 1 && !c.out_f32_nchw && c.Cin % 32 == 0, "conv1x1: not a bf16-output 1x1 conv");
     const int bm = conv_cout_pad(c.Cout) % 128 == 0 && c.Cin <= 64 ? 128 : conv_cout_pad(c.Cout) % 64 == 0 ? 64 : 32;
-    if (c.Cout % (bm / 4) != 0) return false;  // lane groups own bm/4 consecutive couts
+    MVP_REQUIRE(c.Cout % (bm / 4) == 0, "conv1x1: Cout %d", c.Cout);  // lane groups own bm/4 consecutive couts
     const int cout_pad = conv_cout_pad(c.Cout);
     const int kch = c.Cin / 32;
     P1x1 p{c.x, c.w, c.bias, c.res, c.y, conv_zero_region(), (long)c.N * c.H * c.W, c.Cout, c.relu,
@@ -666,14 +648,14 @@ bool launch_conv1x1_direct(const ConvLaunch& c, hipStream_t s) {
         p.c2 = c.Cin - c.c1;
         p.kch1 = c.c1 / 32;
     }
-    if (p.n_pix == 0) return true;
+    if (p.n_pix == 0) return;
     if (cout_pad % 128 == 0 && kch <= 2) {  // 128 couts: registers allow K <= 64
         if (kch == 1) launch_1x1<128, 1>(p, cout_pad, s);
         else launch_1x1<128, 2>(p, cout_pad, s);
-        return true;
+        return;
     }
     if (cout_pad % 64 == 0) return dispatch_k<64>(p, kch, cout_pad, s);
-    return dispatch_k<32>(p, kch, cout_pad, s);
+    dispatch_k<32>(p, kch, cout_pad, s);
 }
 
 }  // namespace mvp

@@ -1,5 +1,6 @@
 // Backbone graph runtime: validation, fusion passes that compile the ops into one launch
-// list, liveness-based arena planning from that list, launch.
+// list, each launch's kernel selected once (kernel_select.h), liveness-based arena planning
+// from that list, launch.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -11,28 +12,16 @@
 namespace mvp {
 namespace {
 
-// The kernel a launch runs; the numbers are mvp_graph_plan's documented route values.
-enum Route {
-    R_BLOCK = 1,      // fused BasicBlock (op - 1, op)
-    R_TWIN = 2,       // transition1: 3x3/s1 conv + its 3x3/s2 twin
-    R_SIBLINGS = 3,   // 3x3/s2 siblings on one input
-    R_HEAD_FUSE = 4,  // heatmap head + the last fuse sum
-    R_BNECK = 5,      // whole Bottleneck
-    R_STEM2 = 6,      // stem conv + conv2
-    R_STEM = 7,
-    R_CONV = 8,       // one conv (possibly cat-fused)
-    R_PAIR = 9,       // Bottleneck join: 1x1 conv (possibly cat-fused) + the next block's conv1
-    R_FUSE_SUM = 10,
-};
-
-// One kernel launch of the forward.  The fusion passes emit these; arena planning, forward,
-// mvp_graph_plan and the derived-weight fill only read them.
+// One kernel launch of the forward.  The fusion passes emit these and select_kernels gives each
+// its kernel; arena planning, forward, mvp_graph_plan / mvp_graph_kernels and the derived-weight
+// fill only read them.
 struct Launch {
-    Route route;
+    Route route;                // what the launch computes (the passes) ...
     int op;                     // launching op: the launch's place in op order (plan records, lifetimes)
     std::vector<int> covers;    // every op it computes, launcher first (R_SIBLINGS: in output order)
     std::vector<int> reads;     // tensors it reads from memory ...
     std::vector<int> writes;    // ... and writes to it; LDS / register intermediates are in neither
+    KernelChoice kernel;        // ... and the kernel that computes it (select_kernels)
     int64_t macs = 0;           // per crop, over covers
     // route parameters (op indices, -1: none)
     int cat_src = -1;           // R_CONV / R_PAIR / lead R_BNECK: absorbed 1x1 whose input and weights are concatenated
@@ -47,7 +36,7 @@ struct Launch {
     // derived weights (owned; alloc_weights / fill_weights / free_weights)
     uint16_t* w = nullptr;      // cat_src: [cout_pad][cin + cin_src]; R_SIBLINGS: [128][3][3][cin]
     float* b = nullptr;         // cat_src: summed biases [cout_pad]; R_SIBLINGS: [128]
-    uint16_t* w_img = nullptr;  // R_CONV: tconv16 image; R_TWIN: trans1 image
+    uint16_t* w_img = nullptr;  // R_CONV: the image its kernel reads (conv_image_elems); R_TWIN: trans1 image
 };
 
 struct Segment {
@@ -65,6 +54,8 @@ struct Graph {
     const uint16_t* wb = nullptr;
     const float* fb = nullptr;
     int max_batch = 0;
+    Switches sw;                   // the environment's, as mvp_graph_create found it
+    int cus = 0;                   // cu_count(): crop-streaming kernels from one crop per CU
     std::vector<Launch> launches;  // in op order once finish_launches has run
     std::vector<int> owner;        // per op: index of the launch that covers it, -1 = none yet
     std::vector<int64_t> offset;   // per-crop-batch arena offsets (bytes), -1 = external
@@ -78,9 +69,33 @@ int64_t tensor_bytes(const mvp_tensor_desc& t, int batch) {
     return (int64_t)batch * t.h * t.w * t.c * elem_size(t.dtype);
 }
 
-bool env_set(const char* name) {
-    const char* e = getenv(name);
-    return e && e[0] == '1';
+// The only reader of the backbone's switches: once per mvp_graph_create.
+Switches read_switches() {
+    auto first_is = [](const char* name, char c) {
+        const char* e = getenv(name);
+        return e && e[0] == c;
+    };
+    Switches sw;
+    sw.no_fuse = first_is("MVPOSE_NO_FUSE", '1');
+    sw.no_catfuse = first_is("MVPOSE_NO_CATFUSE", '1');
+    sw.no_pairfuse = first_is("MVPOSE_NO_PAIRFUSE", '1');
+    sw.no_bneck = first_is("MVPOSE_NO_BNECK", '1');
+    sw.no_stemfuse = first_is("MVPOSE_NO_STEMFUSE", '1');
+    sw.no_transfuse = first_is("MVPOSE_NO_TRANSFUSE", '1');
+    sw.no_sibfuse = first_is("MVPOSE_NO_SIBFUSE", '1');
+    sw.no_headfuse = first_is("MVPOSE_NO_HEADFUSE", '1');
+    sw.no_tblock64 = first_is("MVPOSE_NO_TBLOCK64", '1');
+    sw.no_head1x1 = first_is("MVPOSE_NO_HEAD1X1", '1');
+    sw.no_tconv = first_is("MVPOSE_NO_TCONV", '1');
+    sw.no_tconv16 = first_is("MVPOSE_TCONV16", '0');
+    sw.no_s2conv = first_is("MVPOSE_NO_S2CONV", '1');
+    sw.no_tblock = first_is("MVPOSE_NO_TBLOCK", '1');
+    sw.no_tblock32s = first_is("MVPOSE_NO_TBLOCK32S", '1');
+    sw.stem2_tile = first_is("MVPOSE_STEM2_TILE", '1');
+    sw.crop_stream = first_is("MVPOSE_CROP_STREAM", '1');
+    const char* e = getenv("MVPOSE_S2_TILE");
+    sw.s2_tile = e ? atoi(e) : 0;
+    return sw;
 }
 
 void validate(Graph& g, int64_t w_elems, int64_t f_elems) {
@@ -243,7 +258,8 @@ void fuse(Graph& g) {
         const bool b_res = b.n_in > 1 && b.in[1] == a.in[0];
         const mvp_tensor_desc& t = g.tensors[a.out];
         if (has_res(a) || !b_res || b.in[0] != a.out || ud.uses[a.out] != 1 || a.out == g.output) continue;
-        const bool ok = a.cin == 32 ? basic_block_c32_supported(t.h, t.w) : tblock64_supported(t.h, t.w);
+        const bool ok =
+            a.cin == 32 ? basic_block_c32_supported(t.h, t.w) : !g.sw.no_tblock64 && tblock64_supported(t.h, t.w);
         if (a.segment != b.segment || !ok) continue;
         cover(g, emit(g, R_BLOCK, k + 1, {a.in[0]}, {b.out}), k);
         k++;
@@ -256,6 +272,7 @@ void fuse(Graph& g) {
 // t tensor (256 channels at 64x48 in HRNet-W32: 1.6 GB per 1024 crops, written then read
 // back as the residual) disappears, and t is no longer rounded to bf16 before the add.
 void cat_fuse(Graph& g) {
+    if (g.sw.no_catfuse) return;
     const UseDef ud = use_def(g, true);
     for (int b = 0; b < (int)g.ops.size(); b++) {
         const mvp_op_desc& B = g.ops[b];
@@ -286,7 +303,7 @@ bool bneck_chain(Graph& g, const UseDef& ud, int c, int cin1, int& a, int& b) {
     a = ud.producer[g.ops[b].in[0]];
     if (!mid(a, 1, cin1)) return false;
     const mvp_tensor_desc& x = g.tensors[g.ops[a].in[0]];
-    return bneck_supported(x.h, x.w, x.c, g.ops[a].cout);
+    return !g.sw.no_bneck && bneck_supported(x.h, x.w, x.c, g.ops[a].cout);
 }
 
 // Bottleneck fusion (bneck.hip): layer1's Bottleneck on the 256-ch 64x48 plane — conv1 (1x1
@@ -295,7 +312,8 @@ bool bneck_chain(Graph& g, const UseDef& ud, int c, int cin1, int& a, int& b) {
 // intermediates are never allocated.  Runs before pair_fuse (which would otherwise join conv1
 // to the previous block's conv3); conv1 keeps the K order the join would have given it (perm)
 // so the result stays bit-identical to the unfused graph.
-void bneck_fuse(Graph& g, bool pair_enabled) {
+void bneck_fuse(Graph& g) {
+    const bool pair_enabled = !g.sw.no_pairfuse;
     const int no = (int)g.ops.size();
     const UseDef ud = use_def(g, true);
     int a = -1, b = -1;
@@ -333,6 +351,7 @@ void bneck_fuse(Graph& g, bool pair_enabled) {
 // conv1) runs as one conv1x1_pair launch that writes T (still needed as the next
 // residual) and B's output; T is no longer re-read for B.
 void pair_fuse(Graph& g) {
+    if (g.sw.no_pairfuse) return;
     const UseDef ud = use_def(g, false);
     for (int b = 0; b < (int)g.ops.size(); b++) {
         const mvp_op_desc& B = g.ops[b];
@@ -355,6 +374,7 @@ void pair_fuse(Graph& g) {
 // conv (HRNet's conv2) runs inside that conv's launch (stem2.hip); the 128x96x64 intermediate
 // (1.6 GB per 1024 crops) is never allocated.
 void stem_fuse(Graph& g) {
+    if (g.sw.no_stemfuse) return;
     const int no = (int)g.ops.size();
     const UseDef ud = use_def(g, false);
     for (int a = 0; a < no; a++) {
@@ -378,6 +398,7 @@ void stem_fuse(Graph& g) {
 // Transition fusion: HRNet's transition1 reads the layer1 output (256 ch @ 64x48) with two
 // 3x3 convs (s1 -> 32 ch, s2 -> 64 ch); trans1.hip runs both from one pass over it.
 void twin_fuse(Graph& g) {
+    if (g.sw.no_transfuse) return;
     const int no = (int)g.ops.size();
     for (int a = 0; a < no; a++) {
         if (!is_free(g, a) || !plain_conv(g, a, 3, 1, 1)) continue;
@@ -414,6 +435,7 @@ void planar_fuse(Graph& g) {
 // branches 2 and 3).  They run as ONE launch over cout-concatenated weights (s2conv_multi):
 // the 201 MB input is read once instead of once per conv.
 void sib_fuse(Graph& g) {
+    if (g.sw.no_sibfuse) return;
     const int no = (int)g.ops.size();
     auto plain_s2 = [&](int k) { return is_free(g, k) && plain_conv(g, k, 3, 2, -1) && g.ops[k].cout % 32 == 0; };
     for (int a = 0; a < no; a++) {
@@ -442,6 +464,7 @@ void sib_fuse(Graph& g) {
 // 32 -> 17, f32 NCHW); the head kernel forms out0 per pixel itself, so the 201 MB tensor is
 // never written or re-read (bit-identical: same sums, same bf16 rounding).
 void head_fuse(Graph& g) {
+    if (g.sw.no_headfuse || g.sw.no_head1x1) return;
     const UseDef ud = use_def(g, false);
     for (int k = 0; k < (int)g.ops.size(); k++) {
         const mvp_op_desc& H = g.ops[k];
@@ -496,18 +519,35 @@ void finish_launches(Graph& g) {
     for (int k = 0; k < no; k++) MVP_REQUIRE(covered[k] == 1, "graph: op %d covered by %d launches", k, covered[k]);
 }
 
+// ---- kernel selection -------------------------------------------------------------------------
+
+// What select_kernel looks at (kernel_select.h LaunchShape).
+LaunchShape launch_shape(const Graph& g, const Launch& L) {
+    const mvp_op_desc& op = g.ops[L.op];
+    const mvp_tensor_desc& x = g.tensors[op.in[0]];
+    const bool cat = L.cat_src >= 0;
+    LaunchShape c;
+    c.cin = op.cin + (cat ? g.ops[L.cat_src].cin : 0), c.cout = op.cout, c.h = x.h, c.w = x.w;
+    c.ks = op.ks, c.stride = op.stride, c.relu = op.relu;
+    c.res = !cat && has_res(op);  // a cat-fused launch has its residual in the second input
+    c.f32_out = g.tensors[op.out].dtype == MVP_DT_F32_NCHW;
+    c.cat = cat ? op.cin : 0;
+    return c;
+}
+
+// Every launch's kernel, from its route, its shape and the switches: chosen here once, so the
+// weight images, mvp_graph_kernels and every forward agree on it.  The graph makes the weight
+// image for whichever kernel reads one, hence has_image = true.
+void select_kernels(Graph& g) {
+    for (Launch& L : g.launches) {
+        L.kernel = select_kernel(L.route, launch_shape(g, L), g.sw, true);
+        MVP_REQUIRE(L.kernel.small != K_NONE && L.kernel.stream != K_NONE, "graph op %d: no kernel serves it", L.op);
+    }
+}
+
 // ---- derived weights ---------------------------------------------------------------------
 // Device-side weights a launch owns: allocated at graph create time, filled from the blobs by
 // fill_weights (create and mvp_graph_refresh_weights).
-
-long t16_elems(const Graph& g, const Launch& L) {
-    const mvp_op_desc& op = g.ops[L.op];
-    if (L.route != R_CONV || L.cat_src >= 0 || (op.stride == 1 && !op.relu) ||
-        g.tensors[op.out].dtype == MVP_DT_F32_NCHW)
-        return 0;
-    const mvp_tensor_desc& x = g.tensors[op.in[0]];
-    return tconv16_image_elems(op.cin, op.cout, x.h, x.w, op.ks, op.stride);
-}
 
 void alloc_weights(Graph& g) {
     for (Launch& L : g.launches) {
@@ -521,7 +561,7 @@ void alloc_weights(Graph& g) {
             MVP_HIP(hipMalloc(&L.b, (size_t)128 * sizeof(float)));
         } else if (L.route == R_TWIN) {
             MVP_HIP(hipMalloc(&L.w_img, (size_t)kTrans1ImageElems * sizeof(uint16_t)));
-        } else if (const long n = t16_elems(g, L)) {
+        } else if (const long n = L.route == R_CONV ? conv_image_elems(L.kernel.small, launch_shape(g, L)) : 0) {
             MVP_HIP(hipMalloc(&L.w_img, (size_t)n * sizeof(uint16_t)));
         }
     }
@@ -697,12 +737,12 @@ extern "C" int mvp_graph_create(const mvp_tensor_desc* tensors, int n_tensors, c
         mvp::validate(*g, w_elems, f_elems);
         g->owner.assign(n_ops, -1);
         g->launches.reserve(n_ops);  // the passes hold Launch references across emit()
-        // diagnostics: MVPOSE_NO_FUSE=1 runs every op on its own, MVPOSE_NO_CATFUSE=1 keeps the
-        // downsample conv separate; the kernels' *_supported() read the other switches
-        if (!mvp::env_set("MVPOSE_NO_FUSE")) {
+        g->sw = mvp::read_switches();
+        g->cus = mvp::cu_count();
+        if (!g->sw.no_fuse) {  // each pass looks at its own switch
             mvp::fuse(*g);
-            if (!mvp::env_set("MVPOSE_NO_CATFUSE")) mvp::cat_fuse(*g);
-            mvp::bneck_fuse(*g, mvp::conv1x1_pair_supported(64, 256, 64));
+            mvp::cat_fuse(*g);
+            mvp::bneck_fuse(*g);
             mvp::pair_fuse(*g);
             mvp::stem_fuse(*g);
             mvp::twin_fuse(*g);
@@ -711,6 +751,7 @@ extern "C" int mvp_graph_create(const mvp_tensor_desc* tensors, int n_tensors, c
             mvp::head_fuse(*g);
         }
         mvp::finish_launches(*g);
+        mvp::select_kernels(*g);
         mvp::alloc_weights(*g);
         mvp::fill_weights(*g);
         mvp::plan(*g);
@@ -752,12 +793,19 @@ extern "C" int mvp_graph_forward(void* handle, const void* input_dev, int batch,
         const mvp_op_desc& op = g->ops[L.op];
         const mvp_tensor_desc& o = g->tensors[op.out];
         const mvp_tensor_desc& x = g->tensors[L.reads[0]];
+        const mvp::Kernel kernel = mvp::pick_kernel(L.kernel, nb, g->cus, g->sw);
         switch (L.route) {
         case mvp::R_BLOCK: {
             const mvp_op_desc& c1 = g->ops[L.op - 1];
-            auto launch = c1.cin == 32 ? mvp::launch_basic_block_c32 : mvp::launch_tblock64;
-            launch(bf16(op.in[1]), g->wb + c1.w_off, g->fb + c1.b_off, g->wb + op.w_off, g->fb + op.b_off,
-                   bf16(op.out), nb, o.h, o.w, s);
+            const uint16_t *xb = bf16(op.in[1]), *w1 = g->wb + c1.w_off, *w2 = g->wb + op.w_off;
+            const float *b1 = g->fb + c1.b_off, *b2 = g->fb + op.b_off;
+            uint16_t* y = bf16(op.out);
+            switch (kernel) {
+            case mvp::K_TBLOCK32S: mvp::launch_tblock32s(xb, w1, b1, w2, b2, y, nb, o.h, o.w, s); break;
+            case mvp::K_TBLOCK32: mvp::launch_tblock32(xb, w1, b1, w2, b2, y, nb, o.h, o.w, s); break;
+            case mvp::K_BASIC_BLOCK_C32: mvp::launch_basic_block_c32(xb, w1, b1, w2, b2, y, nb, o.h, o.w, s); break;
+            default: mvp::launch_tblock64(xb, w1, b1, w2, b2, y, nb, o.h, o.w, kernel == mvp::K_TBLOCK64, s);
+            }
             break;
         }
         case mvp::R_TWIN: {  // transition1: this 3x3/s1 conv and its 3x3/s2 sibling, one pass
@@ -804,7 +852,7 @@ extern "C" int mvp_graph_forward(void* handle, const void* input_dev, int batch,
         case mvp::R_STEM2: {  // stem conv1 + this conv2 in one launch
             const mvp_op_desc& st = g->ops[L.stem];
             mvp::launch_stem2(bf16(st.in[0]), g->fb + st.w_off, g->fb + st.b_off, g->wb + op.w_off, g->fb + op.b_off,
-                              bf16(op.out), nb, x.h, x.w, s);
+                              bf16(op.out), nb, x.h, x.w, kernel == mvp::K_STEM2, s);
             break;
         }
         case mvp::R_STEM:
@@ -821,14 +869,22 @@ extern "C" int mvp_graph_forward(void* handle, const void* input_dev, int batch,
             c.yf = c.out_f32_nchw ? (float*)ptr(op.out) : nullptr;
             c.N = nb, c.H = x.h, c.W = x.w;
             c.Cin = op.cin, c.Cout = op.cout, c.ks = op.ks, c.stride = op.stride, c.relu = op.relu;
-            c.w_img = L.w_img;
+            c.w_img = L.w_img, c.s2_tile = g->sw.s2_tile;
             if (L.cat_src >= 0) {  // cat-fused: [in[0], absorbed op's input] x [W | W_absorbed]
                 const mvp_op_desc& a = g->ops[L.cat_src];
                 c.x2 = bf16(a.in[0]), c.c1 = op.cin, c.Cin = op.cin + a.cin;
                 c.w = L.w, c.bias = L.b, c.res = nullptr;
             }
             if (L.route == mvp::R_CONV) {
-                mvp::launch_conv(c, s);
+                switch (kernel) {
+                case mvp::K_HEAD1X1: mvp::launch_head1x1(c, s); break;
+                case mvp::K_CONV1X1_WIDE: mvp::launch_conv1x1_wide(c, s); break;
+                case mvp::K_CONV1X1: mvp::launch_conv1x1_direct(c, s); break;
+                case mvp::K_TCONV: mvp::launch_tconv(c, s); break;
+                case mvp::K_TCONV16: mvp::launch_tconv16(c, s); break;
+                case mvp::K_S2CONV: mvp::launch_s2conv(c, s); break;
+                default: mvp::launch_conv_generic(c, s);
+                }
                 break;
             }
             const mvp_op_desc& b = g->ops[L.tail];  // Bottleneck join: this conv + the next block's conv1
@@ -880,6 +936,25 @@ extern "C" int mvp_graph_plan(void* handle, int batch, int64_t* rec_out, int max
     if (covered_macs_out) *covered_macs_out = total;
     MVP_ABI_END
 }
+
+// The kernel of each launch of one forward of `batch` crops: one id (kernel_select.h Kernel;
+// its name from mvp_graph_kernel_name) per record of mvp_graph_plan, in the same order.  A
+// smaller last micro-batch may run another kernel than the full ones.
+extern "C" int mvp_graph_kernels(void* handle, int batch, int* kernels_out, int max_records, int* n_records) {
+    MVP_ABI_BEGIN
+    Graph* g = static_cast<Graph*>(handle);
+    MVP_REQUIRE(g && kernels_out && n_records, "mvp_graph_kernels: NULL pointer");
+    MVP_REQUIRE(batch > 0 && batch <= g->max_batch, "mvp_graph_kernels: batch %d", batch);
+    int n = 0;
+    mvp::for_each_micro_batch(*g, batch, [&](const mvp::Segment& sg, int64_t, int nb) {
+        for (int l = sg.first_launch; l < sg.end_launch; l++, n++)
+            if (n < max_records) kernels_out[n] = mvp::pick_kernel(g->launches[l].kernel, nb, g->cus, g->sw);
+    });
+    *n_records = n;
+    MVP_ABI_END
+}
+
+extern "C" const char* mvp_graph_kernel_name(int kernel) { return mvp::kernel_name(kernel); }
 
 // The blobs were rewritten in place (e.g. a weight broadcast from rank 0 after the graph was
 // built): re-derive every weight the graph copied out of them at create time.  Blocking.

@@ -339,8 +339,6 @@ void init_s() {
 }  // namespace
 
 bool s2conv_multi_supported(int H, int W, int Cin, int total_cout) {
-    const char* e = getenv("MVPOSE_NO_SIBFUSE");  // diagnostics/tests: one launch per sibling
-    if (e && e[0] == '1') return false;
     return H == 64 && W == 48 && Cin == 32 && total_cout <= 128;
 }
 
@@ -366,28 +364,31 @@ void launch_s2conv_multi(const S2Multi& m, hipStream_t s) {
     MVP_HIP(hipGetLastError());
 }
 
-bool launch_s2conv(const ConvLaunch& c, hipStream_t s) {
-    if (c.ks != 3 || c.stride != 2 || c.out_f32_nchw || c.res || c.x2) return false;
-    const char* e = getenv("MVPOSE_NO_S2CONV");  // diagnostics/tests: fall back to conv_mfma_kernel
-    if (e && e[0] == '1') return false;
+void launch_s2conv(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(c.ks == 3 && c.stride == 2 && !c.out_f32_nchw && !c.res && !c.x2, "s2conv: not a plain 3x3/s2 conv");
     const int ci = c.Cin, co = c.Cout, h = c.H, w = c.W;
     // Planes where the 16-channel items lose to conv_mfma_kernel stay there (tools/s2_bench.py,
     // 1024 crops): stem conv2 64@128x96 (1415 vs 796 us), transition1.1 256@64x48 (1162 vs
     // 1057 us) and 64->64 @32x24 (80 vs 51 us).  Their items carry 16 of a pixel's 64..256
     // channels, so each 128-B line is fetched once per item: L2 cannot hold a tile's lines
     // across its 4..16 items and the gather over-fetches 4x.
-    if (h == 64 && w == 48 && co == 64 && ci == 32)  // fuse 1<-0
-        return launch_s<32, 64, 48, 16, 1, true, 64>(c, s), true;
-    if (h == 32 && w == 24 && co == 128) {  // transition2, fuse 2<-{0,1}
-        if (ci == 32) return launch_s<32, 32, 24, 16, 1, true, 128>(c, s), true;
-        if (ci == 64) return launch_s<64, 32, 24, 16, 1, false, 128>(c, s), true;
-    }
-    if (h == 16 && w == 12 && co % 128 == 0) {  // -> 256 @ 8x6: transition3, fuse 3<-{0,1,2}
-        if (ci == 32) return launch_s<32, 16, 12, 8, 4, false, 128>(c, s), true;
-        if (ci == 64) return launch_s<64, 16, 12, 8, 4, false, 128>(c, s), true;
-        if (ci == 128) return launch_s<128, 16, 12, 8, 4, false, 128>(c, s), true;
-    }
-    return false;
+    const bool p24 = h == 32 && w == 24 && co == 128;     // transition2, fuse 2<-{0,1}
+    const bool p12 = h == 16 && w == 12 && co % 128 == 0;  // -> 256 @ 8x6: transition3, fuse 3<-{0,1,2}
+    if (h == 64 && w == 48 && co == 64 && ci == 32)        // fuse 1<-0
+        launch_s<32, 64, 48, 16, 1, true, 64>(c, s);
+    else if (p24 && ci == 32)
+        launch_s<32, 32, 24, 16, 1, true, 128>(c, s);
+    else if (p24 && ci == 64)
+        launch_s<64, 32, 24, 16, 1, false, 128>(c, s);
+    else if (p12 && ci == 32)
+        launch_s<32, 16, 12, 8, 4, false, 128>(c, s);
+    else if (p12 && ci == 64)
+        launch_s<64, 16, 12, 8, 4, false, 128>(c, s);
+    else if (p12 && ci == 128)
+        launch_s<128, 16, 12, 8, 4, false, 128>(c, s);
+    else
+        fail(MVP_ERR_ARG, "s2conv: unsupported plane %d -> %d @ %dx%d", ci, co, h, w);
+    MVP_HIP(hipGetLastError());
 }
 
 }  // namespace mvp

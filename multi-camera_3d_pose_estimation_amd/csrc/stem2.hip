@@ -581,13 +581,11 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
 }  // namespace
 
 bool stem2_supported(int H, int W, int cin2, int cout2) {
-    const char* e = getenv("MVPOSE_NO_STEMFUSE");  // diagnostics/tests: run the two convs apart
-    if (e && e[0] == '1') return false;
     return H == S2::H && W == S2::W && cin2 == 64 && cout2 == 64;
 }
 
 void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uint16_t* w2, const float* b2,
-                  uint16_t* y, int N, int H, int W, hipStream_t s) {
+                  uint16_t* y, int N, int H, int W, bool crop_ranges, hipStream_t s) {
     MVP_REQUIRE(H == S2::H && W == S2::W, "stem2: input %dx%d is not 256x192", H, W);
     if (N == 0) return;
     static bool attr = false;
@@ -595,8 +593,7 @@ void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uin
         MVP_HIP(hipFuncSetAttribute((const void*)stem2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2S::LDS));
         attr = true;
     }
-    const char* e = getenv("MVPOSE_STEM2_TILE");  // tests: the tile kernel (bit-identical reference)
-    if ((e && e[0] == '1') || !crop_ranges_balanced(N, cu_count())) {  // + small / ragged batches
+    if (!crop_ranges) {  // small / ragged batches: the tile kernel (bit-identical)
         static bool attr_t = false;
         if (!attr_t) {
             MVP_HIP(hipFuncSetAttribute((const void*)stem2_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -322,16 +322,14 @@ __global__ __launch_bounds__(512, 1) void tblock32_kernel(TBParams p) {
 
 }  // namespace
 
-bool launch_tblock32(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
+void launch_tblock32(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
                      uint16_t* y, int N, int H, int W, hipStream_t s) {
     // TH = 16, single-buffered input halo: 82.7 us/conv at 1024 crops vs 91.0 for TH = 8
     // double-buffered (more conv1 recompute and input re-fetch) — tools/conv_bench.py
     using G = TBCfg<48, 16, false>;
     static_assert(TBCfg<48, 16, false, true>::LDS == G::LDS, "paired halo changes only the slot order");
-    if (W != 48 || H % G::TH != 0) return false;
-    const char* e = getenv("MVPOSE_NO_TBLOCK");  // diagnostics/tests: use basic_block_c32_kernel
-    if (e && e[0] == '1') return false;
-    if (N == 0) return true;
+    MVP_REQUIRE(W == 48 && H % G::TH == 0, "tblock32: unsupported plane %dx%d", H, W);
+    if (N == 0) return;
     // input halo planes 2k, 2k+1 interleaved per pixel (each DMA instruction touches half the
     // cache lines: +0.6 % frames/s over plane-major, round 2)
     auto kern = tblock32_kernel<48, 16, false, true>;
@@ -346,7 +344,6 @@ bool launch_tblock32(const uint16_t* x, const uint16_t* w1, const float* b1, con
     const int grid = (int)std::min<long>(tiles, cu_count());
     hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NTH), G::LDS, s, p);
     MVP_HIP(hipGetLastError());
-    return true;
 }
 
 }  // namespace mvp

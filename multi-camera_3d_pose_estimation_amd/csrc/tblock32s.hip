@@ -465,26 +465,21 @@ __global__ __launch_bounds__(512, 1) void tblock32s_kernel(S32Params p) {
 
 }  // namespace
 
-bool launch_tblock32s(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
+void launch_tblock32s(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
                       uint16_t* y, int N, int H, int W, hipStream_t s) {
     using G = S32;
-    if (H != G::H || W != G::W) return false;
-    const char* e = getenv("MVPOSE_NO_TBLOCK32S");  // A/B and tests: the tile kernel (tblock.hip)
-    const char* e2 = getenv("MVPOSE_NO_TBLOCK");    // tests: no 32x32x16 block kernel at all
-    if ((e && e[0] == '1') || (e2 && e2[0] == '1')) return false;
-    if (N == 0) return true;
+    MVP_REQUIRE(H == G::H && W == G::W, "tblock32s: unsupported plane %dx%d", H, W);
+    if (N == 0) return;
     static bool attr = false;
     if (!attr) {
         MVP_HIP(hipFuncSetAttribute((const void*)tblock32s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
         attr = true;
     }
-    if (!crop_ranges_balanced(N, cu_count())) return false;  // small / ragged batch: the tile kernel
     MVP_REQUIRE(N < (1 << 24), "tblock32s: too many crops");
     S32Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N};
     const int grid = std::min(N, cu_count());
     hipLaunchKernelGGL(tblock32s_kernel, dim3(grid), dim3(512), G::LDS, s, p);
     MVP_HIP(hipGetLastError());
-    return true;
 }
 
 }  // namespace mvp

@@ -600,12 +600,11 @@ __global__ __launch_bounds__(256, 1) void tblock64_kernel(TB64Params p) {
 }  // namespace
 
 bool tblock64_supported(int H, int W) {
-    const char* e = getenv("MVPOSE_NO_TBLOCK64");  // A/B and tests: two tconv launches instead
-    return !(e && e[0] == '1') && H == B64::H && W == B64::W;
+    return H == B64::H && W == B64::W;
 }
 
 void launch_tblock64(const uint16_t* x, const uint16_t* w1, const float* b1, const uint16_t* w2, const float* b2,
-                     uint16_t* y, int N, int H, int W, hipStream_t s) {
+                     uint16_t* y, int N, int H, int W, bool crop_ranges, hipStream_t s) {
     using G = B64;
     MVP_REQUIRE(H == G::H && W == G::W, "tblock64: unsupported plane %dx%d", H, W);
     if (N == 0) return;
@@ -620,7 +619,7 @@ void launch_tblock64(const uint16_t* x, const uint16_t* w1, const float* b1, con
     // contiguous crop ranges (conv1 reuses rows across a crop's tiles) from one crop per CU;
     // smaller batches: tiles strided over every CU, every tile computing all 10 rows
     TB64Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N, (int)tiles};
-    if (crop_ranges_balanced(N, cu_count()))
+    if (crop_ranges)
         hipLaunchKernelGGL(tblock64_kernel<false>, dim3(std::min(N, cu_count())), dim3(256), G::LDS, s, p);
     else
         hipLaunchKernelGGL(tblock64_kernel<true>, dim3((int)std::min<long>(tiles, cu_count())), dim3(256), G::LDS, s, p);

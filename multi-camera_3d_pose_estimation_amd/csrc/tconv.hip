@@ -349,37 +349,25 @@ void launch_t(const ConvLaunch& c, hipStream_t s) {
 
 }  // namespace
 
-bool launch_tconv(const ConvLaunch& c, hipStream_t s) {
-    if (c.ks != 3 || c.stride != 1 || c.out_f32_nchw || !c.relu || c.Cout % 32 != 0) return false;
-    const char* e = getenv("MVPOSE_NO_TCONV");  // diagnostics/tests: fall back to the other kernels
-    if (e && e[0] == '1') return false;
+void launch_tconv(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(c.ks == 3 && c.stride == 1 && !c.out_f32_nchw && c.relu, "tconv: not a 3x3/s1 ReLU conv");
     // transition1.0: 256 -> 32 @ 64x48, 32-cout tiles of 768 pixels (8 pixel groups), streamed weights
-    if (c.Cin == 256 && c.Cout == 32 && c.H == 64 && c.W == 48) {
+    if (c.Cin == 256 && c.Cout == 32 && c.H == 64 && c.W == 48)
         launch_t<256, 64, 48, 16, 1, false, 32>(c, s);
-        return true;
-    }
-    if (c.Cout % 64 != 0) return false;
-    if (c.Cin == 64 && c.Cout == 64 && c.H == 32 && c.W == 24) {
+    else if (c.Cin == 64 && c.Cout == 64 && c.H == 32 && c.W == 24)
         launch_t<64, 32, 24, 16, 1, true>(c, s);
-        return true;
-    }
-    if (c.Cin == 64 && c.Cout == 64 && c.H == 64 && c.W == 48) {
+    else if (c.Cin == 64 && c.Cout == 64 && c.H == 64 && c.W == 48)
         launch_t<64, 64, 48, 8, 1, true>(c, s);
-        return true;
-    }
-    if (launch_tconv16(c, s)) return true;  // 128 ch @ 16x12, 256 ch @ 8x6: 128-cout tiles
-    // 128 ch @ 16x12 without a weight image (streamed weights, two crops per tile; the
+    // 128 ch @ 16x12 without tconv16's weight image (streamed weights, two crops per tile; the
     // weight-stationary wsconv.hip it replaced in round 2 measured 86.2 us/conv against this
     // kernel's 87.9 on the plane-major halo, 10,207 -> 10,479 frames/s with the pixel-major one)
-    if (c.Cin == 128 && c.H == 16 && c.W == 12) {
+    else if (c.Cin == 128 && c.Cout % 64 == 0 && c.H == 16 && c.W == 12)
         launch_t<128, 16, 12, 16, 2, false>(c, s);
-        return true;
-    }
-    if (c.Cin == 256 && c.H == 8 && c.W == 6) {
+    else if (c.Cin == 256 && c.Cout % 64 == 0 && c.H == 8 && c.W == 6)
         launch_t<256, 8, 6, 8, 8, false>(c, s);
-        return true;
-    }
-    return false;
+    else
+        fail(MVP_ERR_ARG, "tconv: unsupported plane %d -> %d @ %dx%d", c.Cin, c.Cout, c.H, c.W);
+    MVP_HIP(hipGetLastError());
 }
 
 }  // namespace mvp

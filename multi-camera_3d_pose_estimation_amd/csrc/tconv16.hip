@@ -365,20 +365,7 @@ __global__ void tconv16_pack_kernel(const uint16_t* __restrict__ w, uint16_t* __
     }
 }
 
-bool t16_plane(int cin, int cout, int h, int w) {
-    return (cin == 128 && cout == 128 && h == 16 && w == 12) || (cin == 256 && cout % 128 == 0 && h == 8 && w == 6);
-}
-
 }  // namespace
-
-long tconv16_image_elems(int cin, int cout, int h, int w, int ks, int stride) {
-    // stride 1: this file's planes; stride 2: s2conv.hip's streamed-weight planes (same
-    // [tap][plane][128 couts] item image: transition2 / 3 and the fuse-layer chains' last convs)
-    const bool s1 = stride == 1 && t16_plane(cin, cout, h, w);
-    const bool s2 = stride == 2 && ((h == 32 && w == 24 && cout == 128 && cin == 64) ||
-                                    (h == 16 && w == 12 && cout % 128 == 0 && (cin == 32 || cin == 64 || cin == 128)));
-    return (ks == 3 && (s1 || s2)) ? (long)cout * 9 * cin : 0;
-}
 
 void tconv16_pack_weights(const uint16_t* w, uint16_t* img, int cin, int cout, hipStream_t s) {
     MVP_REQUIRE(cin % 16 == 0 && cout % 128 == 0, "tconv16_pack_weights: cin %d, cout %d", cin, cout);
@@ -386,21 +373,17 @@ void tconv16_pack_weights(const uint16_t* w, uint16_t* img, int cin, int cout, h
     MVP_HIP(hipGetLastError());
 }
 
-bool launch_tconv16(const ConvLaunch& c, hipStream_t s) {
-    if (!c.w_img || c.ks != 3 || c.stride != 1 || c.out_f32_nchw || !c.relu || c.x_stride || c.y_stride ||
-        c.r_stride || c.x2)
-        return false;
-    const char* e = getenv("MVPOSE_TCONV16");  // A/B and tests: 0 = tconv.hip's 64-cout tiles
-    if (e && e[0] == '0') return false;
-    if (c.Cin == 128 && c.Cout == 128 && c.H == 16 && c.W == 12) {
+void launch_tconv16(const ConvLaunch& c, hipStream_t s) {
+    MVP_REQUIRE(c.w_img && c.ks == 3 && c.stride == 1 && !c.out_f32_nchw && c.relu && !c.x_stride && !c.y_stride &&
+                    !c.r_stride && !c.x2,
+                "tconv16: not a dense 3x3/s1 ReLU conv with a weight image");
+    if (c.Cin == 128 && c.Cout == 128 && c.H == 16 && c.W == 12)
         launch_t16<128, 16, 12, 16, 2, 128>(c, s);
-        return true;
-    }
-    if (c.Cin == 256 && c.Cout % 128 == 0 && c.H == 8 && c.W == 6) {
+    else if (c.Cin == 256 && c.Cout % 128 == 0 && c.H == 8 && c.W == 6)
         launch_t16<256, 8, 6, 8, 8, 128>(c, s);
-        return true;
-    }
-    return false;
+    else
+        fail(MVP_ERR_ARG, "tconv16: unsupported plane %d -> %d @ %dx%d", c.Cin, c.Cout, c.H, c.W);
+    MVP_HIP(hipGetLastError());
 }
 
 }  // namespace mvp

@@ -266,8 +266,6 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
 }  // namespace
 
 bool trans1_supported(int H, int W, int C, int cout0, int cout1) {
-    const char* e = getenv("MVPOSE_NO_TRANSFUSE");  // diagnostics/tests: the two convs apart
-    if (e && e[0] == '1') return false;
     return H == T1C<true>::H && W == T1C<true>::W && C == T1C<true>::C && cout0 == 32 && cout1 == 64;
 }
 

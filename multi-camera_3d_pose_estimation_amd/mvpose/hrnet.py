@@ -598,6 +598,18 @@ class ConvGraph:
         assert int(rec[:, 3].sum()) == tot.value == self.macs_per_crop() * batch
         return rec
 
+    def launch_kernels(self, batch: int) -> list[str]:
+        """The kernel each launch of one forward of `batch` crops runs, in launch_plan's record
+        order (mvp_graph_kernels): the kernel function's base name as a kernel trace shows it.
+        The graph chose them when it was constructed, under the switches set then."""
+        cap = 4096
+        ids = np.zeros(cap, np.int32)
+        n = ctypes.c_int()
+        call("mvp_graph_kernels", self._h, int(batch), ctypes.c_void_p(ids.ctypes.data), cap, ctypes.byref(n))
+        if n.value > cap:
+            raise RuntimeError(f"{n.value} launches > {cap}")
+        return [_lib.lib.mvp_graph_kernel_name(int(k)).decode() for k in ids[:n.value]]
+
     def macs_per_crop(self) -> int:
         macs = 0
         for op in self.spec.ops:

@@ -62,8 +62,9 @@ def _run(c, h, w, n, n_blocks, seed, monkeypatch, mode):
     out = torch.empty_like(x).cuda()
     g.run(x.cuda(), out)
     torch.cuda.synchronize()
+    kernels = g.launch_kernels(n)
     g.close()
-    return out.float().cpu(), _reference(sd, x.float(), n_blocks)
+    return out.float().cpu(), _reference(sd, x.float(), n_blocks), kernels
 
 
 @pytest.mark.parametrize("c,h,w", PLANES)
@@ -71,8 +72,9 @@ def test_basic_block_vs_reference(c, h, w, monkeypatch):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     n = 37  # ragged: not a multiple of any tile / grid size
+    kernels = {}
     for mode in MODES:
-        got, ref = _run(c, h, w, n, 2, 3, monkeypatch, mode)
+        got, ref, kernels[mode] = _run(c, h, w, n, 2, 3, monkeypatch, mode)
         assert torch.isfinite(got).all()
         rel = (torch.linalg.vector_norm(got - ref) / torch.linalg.vector_norm(ref)).item()
         mx = (got - ref).abs().max().item()
@@ -80,6 +82,10 @@ def test_basic_block_vs_reference(c, h, w, monkeypatch):
         print(f"C={c} {h}x{w} {mode}: rel L2 {rel:.2e}, max abs {mx:.3e} (max|ref| {scale:.2f})")
         assert rel <= 4e-3
         assert mx <= 3 * scale * 2.0 ** -8
+    # the modes ran different kernels: tconv16 against tconv.hip's 64-cout tiles where both serve
+    # the plane, and the generic kernels against either (tblock64 has no generic mode)
+    assert (kernels["tconv"] != kernels["tconv64"]) == (c in (128, 256)), kernels
+    assert (kernels["generic"] != kernels["tconv"]) == ((c, h) != (64, 32)), kernels
 
 
 @pytest.mark.parametrize("stream", ["1", "0"])
@@ -108,9 +114,10 @@ def test_tblock64_bitwise_equals_two_tconv_launches(n, stream, monkeypatch):
         out = torch.empty_like(x)
         g.run(x, out)
         torch.cuda.synchronize()
-        outs.append((out, g.arena_bytes))
+        outs.append((out, g.arena_bytes, g.launch_kernels(n)))
         g.close()
-    (a, arena_a), (b, arena_b) = outs
+    (a, arena_a, kernels_a), (b, arena_b, kernels_b) = outs
+    assert kernels_a == ["tconv_kernel"] * 4 and kernels_b == ["tblock64_kernel"] * 2
     d = (a.float() - b.float()).abs()
     print(f"tblock64 n={n}: max |fused - unfused| {d.max().item():.3g}, identical {(d == 0).float().mean().item():.6f}, "
           f"arena {arena_b} vs {arena_a}")
@@ -134,7 +141,7 @@ def test_tblock32s_bitwise_equals_tile_kernel(n, monkeypatch):
     spec, xi, yo, _ = hrnet.basic_block_spec(32, 64, 48, seed=17, n_blocks=2)
     gen = torch.Generator().manual_seed(18)
     x = torch.randn((n, 64, 48, 32), generator=gen).bfloat16().cuda()
-    outs = []
+    outs, kernels = [], []
     for off in ("1", "0"):
         monkeypatch.setenv("MVPOSE_NO_TBLOCK32S", off)
         g = hrnet.ConvGraph(spec, xi, yo, max_batch=n)
@@ -142,8 +149,10 @@ def test_tblock32s_bitwise_equals_tile_kernel(n, monkeypatch):
         g.run(x, out)
         torch.cuda.synchronize()
         outs.append(out)
+        kernels.append(g.launch_kernels(n))
         g.close()
     a, b = outs
+    assert kernels == [["tblock32_kernel"] * 2, ["tblock32s_kernel"] * 2]
     d = (a.float() - b.float()).abs()
     print(f"tblock32s n={n}: max |stream - tile| {d.max().item():.3g}, identical {(d == 0).float().mean().item():.6f}")
     assert torch.equal(a, b)
@@ -157,7 +166,8 @@ def test_tconv16_tile_ranges_vs_reference(c, h, w, n, monkeypatch):
     128-cout blocks on a fixed cout block per workgroup, XCD-major tile order)."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    got, ref = _run(c, h, w, n, 1, 21, monkeypatch, "tconv")
+    got, ref, kernels = _run(c, h, w, n, 1, 21, monkeypatch, "tconv")
+    assert kernels == ["tconv16_kernel"] * 2
     assert torch.isfinite(got).all()
     rel = (torch.linalg.vector_norm(got - ref) / torch.linalg.vector_norm(ref)).item()
     mx = (got - ref).abs().max().item()
@@ -273,15 +283,17 @@ def test_stem2_streaming_bitwise_equals_tile_kernel(n, monkeypatch):
     x = torch.zeros((n, 256, 192, 4))
     x[..., :3] = torch.randn((n, 256, 192, 3), generator=gen)
     xb = x.bfloat16().cuda()
-    outs = {}
+    outs, kernels = {}, {}
     for tile in ("1", "0"):
         monkeypatch.setenv("MVPOSE_STEM2_TILE", tile)
         g = hrnet.ConvGraph(spec, xi, yo, max_batch=n)
         out = torch.full((n, 64, 48, 64), float("nan"), dtype=torch.bfloat16, device="cuda")
         g.run(xb, out)
         torch.cuda.synchronize()
+        kernels[tile] = g.launch_kernels(n)
         g.close()
         outs[tile] = out.cpu()
+    assert kernels == {"1": ["stem2_tile_kernel"], "0": ["stem2_kernel"]}
     assert torch.isfinite(outs["0"].float()).all()
     assert torch.equal(outs["0"].view(torch.int16), outs["1"].view(torch.int16))
 

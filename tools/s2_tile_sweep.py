@@ -16,11 +16,11 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
 VARIANTS = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else list(range(7))
 for cin, cout, h, w in [(64, 64, 128, 96), (256, 64, 64, 48), (32, 32, 64, 48), (64, 64, 32, 24), (32, 32, 32, 24)]:
     spec, xi, yo, _ = hrnet.conv_spec(cin, cout, h, w, k=3, stride=2, relu=True, seed=1)
-    g = hrnet.ConvGraph(spec, xi, yo, max_batch=n)
     x = torch.randn((n, h, w, cin), device="cuda").bfloat16()
     ref = None
     for v in VARIANTS:
         os.environ["MVPOSE_S2_TILE"] = str(v)
+        g = hrnet.ConvGraph(spec, xi, yo, max_batch=n)  # a graph reads the switches when it is built
         y = torch.empty((n, h // 2, w // 2, cout), device="cuda", dtype=torch.bfloat16)
         for _ in range(3):
             g.run(x, y)
@@ -37,4 +37,4 @@ for cin, cout, h, w in [(64, 64, 128, 96), (256, 64, 64, 48), (32, 32, 64, 48), 
         flop = 2.0 * n * (h // 2) * (w // 2) * cout * cin * 9
         print(f"{cin:3d}->{cout:3d} {h:3d}x{w:<3d} tile{v}: {us:7.1f} us {flop / us / 1e6:6.1f} TFLOP/s "
               f"maxdiff {d:.3g}", flush=True)
-    g.close()
+        g.close()
