@@ -450,9 +450,20 @@ int mvp_det_tensor_copy(void* handle, int t, int n, void* buf_dev, int to_arena,
  * the next conv reading its tensor (a DET_UP2 then launches nothing and leaves its output slice
  * unwritten; a DET_CA computes its scales and leaves its tensor unscaled); folded_out[0] = 2
  * when the letterbox runs inside the stem (op 0 stages its rows from the raw frames; the input
- * tensor stays unwritten unless mvp_det_forward is given letterboxed_dev); else 0.  Off with
- * MVPOSE_DET_FOLD=0 in the environment at create time.  Results are bit-identical either way. */
+ * tensor stays unwritten unless mvp_det_forward is given letterboxed_dev); else 0.  Results are
+ * bit-identical either way.  The switch that turns folding off is one of the detector's
+ * MVPOSE_DET_* switches, all documented in one place: DetSwitches in csrc/det_select.h. */
 int mvp_det_folded_ops(void* handle, int* folded_out, int n_ops);
+/* Diagnostics: the kernel variant of every launch of one mvp_det_forward (letterboxed_dev NULL),
+ * in launch order: the letterbox when it is not folded into the stem, each op's kernel (a DET_CA
+ * launches its pool and fc passes and, unless folded, its scale pass; a folded DET_UP2 nothing),
+ * then the per-frame selection.  mvp_det_create chooses every op's variant from its shape, the
+ * folds, the device's CU count and the MVPOSE_DET_* switches as the environment had them then;
+ * no later change of the environment reaches a live handle.  *n_records = the launches;
+ * kernels_out receives them when max_records (0: count only) has room.  mvp_det_kernel_name: the
+ * variant's name ("" for an unknown id; the variants are DetKernel in csrc/det_select.h). */
+int mvp_det_kernels(void* handle, int* kernels_out, int max_records, int* n_records);
+const char* mvp_det_kernel_name(int kernel);
 int mvp_det_destroy(void* handle);
 
 /* ---------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 // Person detector, the band-halo conv (3x3/s1, >= 96 input channels, 80x80 / 40x40 planes) and
-// its weight image.  Launched by launch_det_conv_gemm (det.hip) through det_launch_band;
-// detnet.cpp asks det_band_eligible and packs the weights.
+// its weight image.  Launched by detnet.cpp through det_launch_band for the ops selected
+// onto it (det_select.h), whose weights detnet.cpp packs.
 #include "det_common.h"
 
 namespace mvp {
@@ -246,13 +246,6 @@ __global__ __launch_bounds__(256) void det_pack_band_kernel(const uint16_t* __re
 
 }  // namespace
 
-bool det_band_eligible(int H, int W, int cin, int npad, int ks, int stride) {
-    return ks == 3 && stride == 1 && H == W && (W == 80 || W == 40) && cin % 32 == 0 && cin / 32 >= 3 &&
-           npad % 32 == 0 && npad <= 32 * kBandBN;
-}
-
-int det_band_rows(int npad) { return (npad + kBandBN - 1) / kBandBN * kBandBN; }
-
 void det_pack_band_weights(const uint16_t* w, uint16_t* img, int npad, int cin, hipStream_t s) {
     MVP_REQUIRE(npad % 32 == 0 && cin % 32 == 0, "det_pack_band_weights: npad %d, cin %d", npad, cin);
     hipLaunchKernelGGL(det_pack_band_kernel, dim3(512), dim3(256), 0, s, w, img, npad, cin);
@@ -269,10 +262,8 @@ void launch_band(const GParams& p, const uint16_t* wband, hipStream_t s) {
 }  // namespace
 
 void det_launch_band(const GParams& p, int n, const uint16_t* wband, bool waves4, hipStream_t s) {
-    if (n == 0) return;
     GParams pb = p;
     pb.n_nb = det_band_rows(p.npad) / kBandBN;
-    MVP_REQUIRE((long)n * p.H / (p.W == 80 ? 4 : 8) < (1L << 24), "det band conv: too many bands");
     // 8 waves (two per SIMD) by default: 22.30 vs 23.33 ms per 128-frame forward with 4
     // (gpurun_out/detband5); MVPOSE_DET_BAND=4 keeps the 4-wave form (tests: bit-identical)
     if (p.W == 80) waves4 ? launch_band<80, 4, 4>(pb, wband, s) : launch_band<80, 4, 8>(pb, wband, s);

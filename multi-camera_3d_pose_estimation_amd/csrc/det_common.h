@@ -1,48 +1,16 @@
-// Internal to the person detector's translation units (det.hip and det_*.hip; not seen by
-// detnet.cpp, whose interface is det.h): the conv parameter block, the device helpers the kernel
-// families share, the host helpers of their launchers, and the per-family conv entry points that
-// launch_det_conv_gemm (det.hip) routes to.
+// Internal to the person detector's kernel translation units (det_*.hip; not seen by detnet.cpp,
+// whose interface is det.h): the device helpers the kernel families share and the host helpers of
+// their launchers.
 #pragma once
 #include <algorithm>
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 #include "conv.h"
 #include "det.h"
 #include "mvp_common.h"
 
-#ifndef DET_HALO_TR
-#define DET_HALO_TR 4  // output rows per halo tile (2, 4 or 8)
-#endif
-
 namespace mvp {
-
-// A detector conv as every conv kernel family takes it (built by launch_det_conv_gemm)
-struct GParams {
-    const uint16_t* x;
-    const uint16_t* w;  // [npad][KS*KS*cin]
-    const float* bias;  // [npad]
-    const uint16_t* res;
-    uint16_t* y;
-    const uint16_t* zero;  // >= 16 KiB of zeros
-    long M;                // n * Ho * Wo
-    int cin, N, npad, xs, ys, rs, act, n_nb;
-    int xcd_order;         // GEMM kernel: XCD-contiguous logical block order
-    int H, W, Ho, Wo;
-    // GEMM kernel: w re-laid by det_pack_gemm_weights (per 32-channel K step, every cout's
-    // four swizzled 16-B chunks in LDS slot order: a weight DMA instruction reads 1 KB
-    // contiguous instead of 16 rows x 64 B); nullptr: gather from w
-    const uint16_t* wimg = nullptr;
-    // persistent 1x1 GEMM folds (DetConvFold, det.h): input channels [0, up_c) from the nearest-2x
-    // upsample of `up` (an H/2 x W/2 plane, pixel stride up_s); `ca`: [n][cin] f32 channel scales
-    const uint16_t* up = nullptr;
-    const float* ca = nullptr;
-    int up_s = 0, up_c = 0;
-};
-
-constexpr int kPersMaxN = 1024;  // couts whose biases the persistent 1x1 kernel stages in LDS
-constexpr int kBandBN = 64;      // couts per work item of the band-halo kernel
 
 // ---------------------------------------------------------------------------- device helpers
 namespace {
@@ -196,19 +164,8 @@ __device__ __forceinline__ void buffer_store_u2v(u32x2 v, i32x4 r, int off) {
 }  // namespace
 
 // ---------------------------------------------------------------------------- host helpers
-// Functions shared between the detector's translation units stay out of libmvpose.so's dynamic
-// symbols (what the library exports of the detector is det.h and the C-ABI).
-#define DET_LOCAL __attribute__((visibility("hidden")))
-
-// First character of an environment switch, 0 if it is unset or empty.  Read at every launch:
-// the tests flip the switches between forwards of one process.
-DET_LOCAL inline char det_env(const char* name) {
-    const char* e = getenv(name);
-    return e ? e[0] : 0;
-}
-
 // one workgroup per CU, a multiple of 8 (the XCD round robin of blockIdx)
-DET_LOCAL inline int det_band_grid() { return std::max(8, cu_count() / 8 * 8); }
+DET_LOCAL inline int det_band_grid() { return det_cu_grid(cu_count()); }
 
 // Grid of a persistent kernel over `items` work items with `occ` workgroups per CU: one workgroup
 // per item, or a multiple of 8 (the kernels' per-XCD split needs one of the two)
@@ -230,19 +187,5 @@ DET_LOCAL void det_dyn_lds(int bytes) {
     }();
     (void)done;
 }
-
-// ---------------------------------------------------------------------------- conv routes
-// The per-family entry points of launch_det_conv_gemm (det.hip), which has checked the arguments
-// and built p; each picks its kernel instance and launches it.  n: frames; live: couts with
-// non-zero weights or bias; blocks: 128-pixel tiles x cout blocks.
-DET_LOCAL void det_launch_band(const GParams& p, int n, const uint16_t* wband, bool waves4, hipStream_t s);  // det_band.hip
-DET_LOCAL void det_launch_halo(const GParams& p, int n, int live, hipStream_t s);                            // det_halo.hip
-// det_gemm.hip: the cout tile of the GEMM kernels, the shapes the fold kernels take (no
-// environment: the graph decided at create time), and the three GEMM routes
-DET_LOCAL int det_conv_bn(int npad);
-DET_LOCAL bool det_fold_shape_ok(int H, int W, int cin, int N, int ks, bool ca);
-DET_LOCAL void det_launch_fold(const GParams& p, int fm, long blocks, hipStream_t s);
-DET_LOCAL void det_launch_pers(const GParams& p, int ks, int stride, long blocks, hipStream_t s);
-DET_LOCAL void det_launch_gemm(const GParams& p, int ks, int stride, long blocks, hipStream_t s);
 
 }  // namespace mvp

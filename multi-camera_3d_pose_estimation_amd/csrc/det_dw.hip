@@ -394,6 +394,5 @@ void launch_det_dwpw(const uint16_t* x, int xs, const float* dw_w, const float* 
 // (4 x 16 tiles) vs 2.73 for dw5 + GEMM; 96 on 80x80 0.90 vs 1.20 (with the identity); with 8 x 8
 // tiles 192 on 40x40 1.00 vs 0.68 and 384 on 20x20 1.12 vs 0.38 — the tile re-reads the whole
 // C x C weight matrix and too few tiles hide the serial phases — so only 64 and 96 are fused.
-bool det_dwpw_supported(int C) { return C == 64 || C == 96; }
 
 }  // namespace mvp

@@ -1,7 +1,7 @@
 // Person detector, conv as GEMM: the im2col GEMM kernel (any 1x1, 3x3/s1 or 3x3/s2 conv), the
 // persistent GEMM with its upsample / channel-attention folds, and their weight image.  Launched by
-// launch_det_conv_gemm (det.hip) through det_launch_fold / _pers / _gemm; detnet.cpp packs the
-// weights and asks det_conv_fold_ok.
+// detnet.cpp through det_launch_fold / _pers / _gemm for the ops whose selected variant
+// (det_select.h) is one of theirs; detnet.cpp packs those ops' weights.
 #include "det_common.h"
 
 namespace mvp {
@@ -544,25 +544,6 @@ void det_pack_gemm_weights(const uint16_t* w, uint16_t* img, int npad, int K, hi
     MVP_HIP(hipGetLastError());
 }
 
-// cout tile: the widest of 192 / 128 / 96 / 64 dividing the padded couts, else 32
-int det_conv_bn(int npad) {
-    return npad % 192 == 0 ? 192 : npad % 128 == 0 ? 128 : npad % 96 == 0 ? 96 : npad % 64 == 0 ? 64 : 32;
-}
-
-bool det_fold_shape_ok(int H, int W, int cin, int N, int ks, bool ca) {
-    if (ks != 1 || N > kPersMaxN || cin % 32 != 0) return false;
-    const int bn = det_conv_bn(det_cout_pad(N));
-    if (bn != 192 && bn != 96) return false;  // the instantiated fold kernels
-    // a 128-pixel tile's rows span at most 8 frames (the scale table)
-    const long hw = (long)H * W;
-    return hw > 0 && (!ca || (127 + hw - 1) / hw + 1 <= 8);
-}
-
-bool det_conv_fold_ok(int H, int W, int cin, int N, int ks, bool ca) {
-    return det_env("MVPOSE_DET_FOLD") != '0' && det_env("MVPOSE_DET_PERS") != '0' &&
-           det_fold_shape_ok(H, W, cin, N, ks, ca);
-}
-
 namespace {
 // the cout tile det_conv_bn chose, as a constant: f(det_int<BN>)
 template <typename F>
@@ -586,28 +567,24 @@ void by_ks_stride(int ks, int stride, F&& f) {
 template <int BN>
 constexpr int kPersPW = (BN == 96 || BN == 32) ? 2 : 1;
 
-// the persistent GEMM's grid: MVPOSE_DET_PERS_OCC (A/B) = workgroups per CU (default 2)
-dim3 pers_grid(long blocks) {
-    const char* eo = getenv("MVPOSE_DET_PERS_OCC");
-    return dim3((unsigned)det_pers_grid(blocks, eo ? std::max(1, atoi(eo)) : 2));
-}
+// the persistent GEMM's grid over the conv's (tile, cout block) items, occ workgroups per CU
+dim3 pers_grid(const GParams& p, int occ) { return dim3((unsigned)det_pers_grid(det_gemm_blocks(p.M, p.npad), occ)); }
 }  // namespace
 
-void det_launch_fold(const GParams& p, int fm, long blocks, hipStream_t s) {
-    const dim3 grid = pers_grid(blocks);
+void det_launch_fold(const GParams& p, DetKernel variant, int occ, hipStream_t s) {
+    const dim3 grid = pers_grid(p, occ);
     by_bn(det_conv_bn(p.npad), [&](auto bn) {
         constexpr int BN = decltype(bn)::value, PW = kPersPW<BN>;
         if constexpr (BN == 192 || BN == 96) {  // the instantiated fold kernels (det_fold_shape_ok)
-            if (fm == 1) hipLaunchKernelGGL((det_conv1x1_pers_kernel<BN, PW, 3, 1, 1, 1>), grid, dim3(256), 0, s, p);
+            if (variant == DK_FOLD_UP) hipLaunchKernelGGL((det_conv1x1_pers_kernel<BN, PW, 3, 1, 1, 1>), grid, dim3(256), 0, s, p);
             else hipLaunchKernelGGL((det_conv1x1_pers_kernel<BN, PW, 3, 1, 1, 2>), grid, dim3(256), 0, s, p);
         }
     });
     MVP_HIP(hipGetLastError());
 }
 
-void det_launch_pers(const GParams& p, int ks, int stride, long blocks, hipStream_t s) {
-    const dim3 grid = pers_grid(blocks);
-    MVP_REQUIRE(grid.x > 0, "det conv: persistent grid");
+void det_launch_pers(const GParams& p, int ks, int stride, int occ, hipStream_t s) {
+    const dim3 grid = pers_grid(p, occ);
     by_ks_stride(ks, stride, [&](auto k, auto st) {
         by_bn(det_conv_bn(p.npad), [&](auto bn) {
             constexpr int BN = decltype(bn)::value, KS = decltype(k)::value, STR = decltype(st)::value;
@@ -617,7 +594,8 @@ void det_launch_pers(const GParams& p, int ks, int stride, long blocks, hipStrea
     MVP_HIP(hipGetLastError());
 }
 
-void det_launch_gemm(const GParams& p, int ks, int stride, long blocks, hipStream_t s) {
+void det_launch_gemm(const GParams& p, int ks, int stride, hipStream_t s) {
+    const long blocks = det_gemm_blocks(p.M, p.npad);
     by_ks_stride(ks, stride, [&](auto k, auto st) {
         by_bn(det_conv_bn(p.npad), [&](auto bn) {
             constexpr int BN = decltype(bn)::value, KS = decltype(k)::value, STR = decltype(st)::value;

@@ -1,6 +1,6 @@
 // Person detector, the halo-tile convs (3x3/s1, 32 or 64 input channels, <= 64 couts): one tile
 // per workgroup, and the persistent form with the weights resident in LDS.  Launched by
-// launch_det_conv_gemm (det.hip) through det_launch_halo.
+// detnet.cpp through det_launch_halo with the variant mvp_det_create selected (det_select.h).
 #include "det_common.h"
 
 namespace mvp {
@@ -306,9 +306,6 @@ __global__ __launch_bounds__(512, 1) void det_conv_halo_pers_kernel(GParams p) {
 
 }  // namespace
 
-// the persistent halo kernel (A/B and tests: MVPOSE_DET_HALO_PERS=0 = det_conv_halo_kernel)
-bool halo_pers_on() { return det_env("MVPOSE_DET_HALO_PERS") != '0'; }
-
 namespace {
 // the conv's cout tile (npad 32 | 64) and 32-channel input chunks (cin 32 | 64), as constants:
 // f(det_int<BN>, det_int<NCK>)
@@ -330,30 +327,22 @@ void launch_halo_pers(const GParams& p, int n, hipStream_t s) {
 }
 }  // namespace
 
-void det_launch_halo(const GParams& p, int n, int live, hipStream_t s) {
-    const int tr = det_env("MVPOSE_DET_HALO_ROWS") == '2' ? 2 : DET_HALO_TR;  // tests: 2 = the 2-row tiles
+void det_launch_halo(const GParams& p, int n, DetKernel variant, hipStream_t s) {
+    const int tr = variant == DK_HALO_2ROW ? 2 : DET_HALO_TR;
     const long tiles = (long)n * ((p.H + tr - 1) / tr) * ((p.W + 63) / 64);
-    MVP_REQUIRE(tiles < (1L << 31), "det conv: grid too large");
-    if (tiles == 0) return;
-    const bool pers = !p.res && halo_pers_on();
-    // 48 real couts in 64 (RTMDet-m stem.2, stage-1 conv1): 3 live tiles
-    const bool live3 = live <= 48 && live > 32 && !p.res && DET_HALO_TR % 4 == 0 && det_env("MVPOSE_DET_LIVE") != '0';
     by_npad_cin(p.npad, p.cin, [&](auto bn, auto nck) {
         constexpr int BN = decltype(bn)::value, NCK = decltype(nck)::value;
         auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(256), 0, s, p); };
-        if (tr == 2) {
+        if (variant == DK_HALO_2ROW) {
             go(det_conv_halo_kernel<BN, NCK, 2>);
-        } else if constexpr (BN == 64) {
-            if (live == 48 && pers) launch_halo_pers<64, NCK, 3>(p, n, s);
-            else if (live == 64 && pers) launch_halo_pers<64, NCK, 4>(p, n, s);
-            else if (live3) go(det_conv_halo_kernel<64, NCK, DET_HALO_TR, 3>);
-            else go(det_conv_halo_kernel<64, NCK, DET_HALO_TR>);
+        } else if (variant == DK_HALO) {
+            go(det_conv_halo_kernel<BN, NCK, DET_HALO_TR>);
+        } else if constexpr (BN == 64) {  // the variants select_det_conv gives the 64-cout convs only
+            if (variant == DK_HALO_PERS_LT3) launch_halo_pers<64, NCK, 3>(p, n, s);
+            else if (variant == DK_HALO_PERS_LT4) launch_halo_pers<64, NCK, 4>(p, n, s);
+            else go(det_conv_halo_kernel<64, NCK, DET_HALO_TR, 3>);  // DK_HALO_LIVE3
         } else if constexpr (NCK == 1) {
-            // RTMDet-m stem.1 (24 -> 24 couts stored as 32): both 16-cout tiles live
-            if (live > 16 && pers) launch_halo_pers<32, 1, 2>(p, n, s);
-            else go(det_conv_halo_kernel<32, 1, DET_HALO_TR>);
-        } else {
-            go(det_conv_halo_kernel<32, 2, DET_HALO_TR>);
+            launch_halo_pers<32, 1, 2>(p, n, s);  // DK_HALO_PERS_LT2
         }
     });
     MVP_HIP(hipGetLastError());

@@ -211,7 +211,6 @@ __global__ __launch_bounds__(256) void det_head_kernel(HeadParams p) {
 // xs elements apart, so one lane per pixel made every 16-B load instruction touch 64 rows
 // (2.3 TB/s).  Here the workgroup's 256 pixels x 32 + 32 channels arrive as 64-B runs per
 // pixel (coalesced), then each lane runs the same fmaf chains in the same k order.
-constexpr int kHeadKC = 32;  // channels of cls and of reg per staging step
 
 __global__ __launch_bounds__(256) void det_head_staged_kernel(HeadParams p) {
 #pragma clang fp contract(off)  // box arithmetic rounded op by op, as mmdet's torch ops
@@ -439,7 +438,7 @@ void launch_det_ca(uint16_t* x, int xs, int n, int HW, int C, const float* wt, c
     hipLaunchKernelGGL(ca_fc_kernel, dim3((unsigned)((C + 63) / 64), (unsigned)n), dim3(64), (size_t)C * sizeof(float),
                        s, p);
     MVP_HIP(hipGetLastError());
-    if (!scale_pass) return;  // folded into the consumer conv (DetConvFold::ca)
+    if (!scale_pass) return;  // folded into the consumer conv (GParams::ca)
     const long work = (long)HW * (C / 8);
     hipLaunchKernelGGL(ca_scale_kernel, dim3((unsigned)((work + 255) / 256), (unsigned)n), dim3(256), 0, s, x, sc, HW,
                        C, xs);
@@ -472,13 +471,13 @@ void launch_det_up2(const uint16_t* x, int xs, uint16_t* y, int ys, int n, int H
 }
 
 void launch_det_head(const uint16_t* x, int xs, int F, const float* w, const float* b, float* cand, int n, int H, int W,
-                     int stride, int size, int n_priors, int prior0, hipStream_t s) {
+                     int stride, int size, int n_priors, int prior0, bool direct, hipStream_t s) {
     MVP_REQUIRE(F % 8 == 0 && xs >= 2 * F && prior0 + H * W <= n_priors, "det head: shape");
     HeadParams p{x, w, b, cand, H, W, F, xs, stride, size, n_priors, prior0};
     if (n == 0) return;
     const dim3 grid((unsigned)((H * W + 255) / 256), (unsigned)n);
-    // MVPOSE_DET_HEAD_DIRECT (tests): 1 = one lane per pixel from HBM
-    if (F % kHeadKC == 0 && det_env("MVPOSE_DET_HEAD_DIRECT") != '1')
+    // direct: one lane per pixel from HBM
+    if (!direct)
         hipLaunchKernelGGL(det_head_staged_kernel, grid, dim3(256),
                            (size_t)((5 * F + 3) & ~3) * sizeof(float) + 256 * 9 * sizeof(uint4), s, p);
     else

@@ -2,7 +2,9 @@
 // launch.  The op list comes from the host builder (mvpose/rtmdet.py); tensors are bf16
 // NHWC per image, ops address channel slices ("views") so every concatenation of the
 // network (CSP layers, SPP, the PAFPN's top-down / bottom-up joins, the head's cls/reg
-// pair) is a shared buffer its producers write into.
+// pair) is a shared buffer its producers write into.  mvp_det_create reads the MVPOSE_DET_*
+// switches once (read_det_switches), plans the folds and selects every op's kernel
+// (det_select.h); run_ops launches what was selected.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -24,9 +26,12 @@ struct DetNet {
     int64_t arena_bytes = 0;
     char* arena = nullptr;
     float* ca_scratch = nullptr;
-    std::vector<uint16_t*> wimg;   // per conv op: the GEMM kernel's weight image (owned)
-    std::vector<uint16_t*> wband;  // per band-eligible conv op: the band kernel's weight image (owned)
-    // producer passes folded into their consumer 1x1 conv (det.h DetConvFold; plan_folds)
+    DetSwitches sw;                 // the environment at mvp_det_create
+    std::vector<DetKernel> kernel;  // per op: the variant it launches (select_kernels)
+    // per op: the weight image its kernel reads (det_image_elems; owned), wimg for the GEMM
+    // kernels and dwpw, wband for the band kernel; nullptr: the kernel reads the blob
+    std::vector<uint16_t*> wimg, wband;
+    // producer passes folded into their consumer 1x1 conv (det.h GParams::up / ca; plan_folds)
     std::vector<int> fold_src;  // per conv op: the DET_UP2 / DET_CA op folded into it, or -1
     std::vector<char> folded;   // per op: its pass runs inside its consumer (UP2: not launched; CA: no scale pass)
     bool lb_folded = false;     // the letterbox runs inside op 0 (the stem stages its rows from the frames)
@@ -43,6 +48,27 @@ void free_det(DetNet& g) {
     g.ca_scratch = nullptr;
     g.wimg.clear();
     g.wband.clear();
+}
+
+// The only reader of the detector's environment switches (det_select.h DetSwitches).
+DetSwitches read_det_switches() {
+    auto env = [](const char* name) -> const char* { return getenv(name); };
+    auto first = [&](const char* name) -> char {  // first character, 0 if unset or empty
+        const char* e = env(name);
+        return e ? e[0] : 0;
+    };
+    DetSwitches sw;
+    sw.xcd = first("MVPOSE_DET_XCD") != '0';
+    const char band = first("MVPOSE_DET_BAND"), pers = first("MVPOSE_DET_PERS");
+    sw.band = band == '0' ? 0 : band == '4' ? 4 : 1;
+    sw.pers = pers == '0' ? 0 : pers == '3' ? 3 : 1;
+    if (const char* occ = env("MVPOSE_DET_PERS_OCC")) sw.pers_occ = std::max(1, atoi(occ));
+    sw.fold = first("MVPOSE_DET_FOLD") != '0';
+    sw.halo_pers = first("MVPOSE_DET_HALO_PERS") != '0';
+    sw.halo_rows2 = first("MVPOSE_DET_HALO_ROWS") == '2';
+    sw.live = first("MVPOSE_DET_LIVE") != '0';
+    sw.head_direct = first("MVPOSE_DET_HEAD_DIRECT") == '1';
+    return sw;
 }
 
 int64_t per_image_bytes(const mvp_tensor_desc& t) { return (int64_t)t.h * t.w * t.c * 2; }
@@ -218,16 +244,18 @@ void plan(DetNet& g) {
 // half-resolution source instead), and a DET_CA directly followed by the 1x1 conv on its tensor
 // (every CSP layer's final_conv: the scales are applied as the pixels land in LDS).  Each stays
 // unfolded unless nothing else reads the bytes the fold leaves unwritten or unscaled.
-// MVPOSE_DET_FOLD=0 (read here) keeps every producer pass.
+// DetSwitches::fold off keeps every producer pass; the conv folds need the persistent GEMM
+// (DetSwitches::pers).
 void plan_folds(DetNet& g) {
     const int no = (int)g.ops.size();
     g.fold_src.assign(no, -1);
     g.folded.assign(no, 0);
     g.lb_folded = false;
-    {
-        const char* e = getenv("MVPOSE_DET_FOLD");
-        if (e && e[0] == '0') return;
-    }
+    if (!g.sw.fold) return;
+    auto conv_takes_fold = [&](const mvp_det_op& c, bool ca) {
+        const mvp_tensor_desc& x = g.tensors[c.in.t];
+        return g.sw.pers != 0 && det_fold_shape_ok(x.h, x.w, c.in.c, c.out.c, c.ks, ca);
+    };
     // the letterbox into the stem: op 0 is the only reader of the letterboxed input
     g.lb_folded = g.ops[0].kind == MVP_DET_STEM;
     for (int k = 1; k < no; k++) {
@@ -254,10 +282,9 @@ void plan_folds(DetNet& g) {
             while (j < no && !reads(g.ops[j], t)) j++;
             if (j == no) continue;
             const mvp_det_op& c = g.ops[j];
-            const mvp_tensor_desc& x = g.tensors[c.in.t];
             if (c.kind != MVP_DET_CONV || c.ks != 1 || c.in.t != t || c.in.coff != 0 || u.out.coff != 0 ||
                 u.out.c % 32 != 0 || u.out.c > c.in.c || c.res.t == t || g.tensors[u.in.t].c % 8 != 0 ||
-                !det_conv_fold_ok(x.h, x.w, c.in.c, c.out.c, 1, false))
+                !conv_takes_fold(c, false))
                 continue;
             bool ok = true;
             for (int m = 0; m < no && ok; m++) {
@@ -272,9 +299,8 @@ void plan_folds(DetNet& g) {
             g.fold_src[j] = k;
         } else if (u.kind == MVP_DET_CA && k + 1 < no) {
             const mvp_det_op& c = g.ops[k + 1];
-            const mvp_tensor_desc& x = g.tensors[u.in.t];
             if (c.kind != MVP_DET_CONV || c.ks != 1 || c.in.t != u.in.t || c.in.coff != u.in.coff || c.in.c != u.in.c ||
-                c.res.t == u.in.t || !det_conv_fold_ok(x.h, x.w, c.in.c, c.out.c, 1, true))
+                c.res.t == u.in.t || !conv_takes_fold(c, true))
                 continue;
             bool ok = true;
             for (int m = k + 2; m < no && ok; m++)
@@ -282,6 +308,70 @@ void plan_folds(DetNet& g) {
             if (!ok) continue;
             g.folded[k] = 1;
             g.fold_src[k + 1] = k;
+        }
+    }
+}
+
+DetOpShape op_shape(const DetNet& g, int k) {
+    const mvp_det_op& op = g.ops[k];
+    const mvp_tensor_desc& x = g.tensors[op.in.t];
+    DetOpShape c;
+    c.kind = op.kind, c.h = x.h, c.w = x.w, c.cin = op.in.c, c.cout = op.out.t >= 0 ? op.out.c : 0;
+    c.ks = op.ks, c.stride = op.stride;
+    const bool conv = op.kind == MVP_DET_CONV;
+    c.live = conv ? (int)op.aux : 0;
+    c.res = (conv || op.kind == MVP_DET_DWPW) && op.res.t >= 0;
+    return c;
+}
+
+DetFold op_fold(const DetNet& g, int k) {
+    if (k == 0 && g.lb_folded) return DF_LETTERBOX;
+    if (g.fold_src[k] < 0) return DF_NONE;
+    return g.ops[g.fold_src[k]].kind == MVP_DET_UP2 ? DF_UP : DF_CA;
+}
+
+// Every op's kernel, and what its launcher needs of the shapes, checked once for up to max_batch
+// frames (plan_folds runs first).  A graph no kernel serves fails here, not at its first forward.
+void select_kernels(DetNet& g, int cus) {
+    const int no = (int)g.ops.size();
+    const long nmax = g.max_batch;
+    g.kernel.assign(no, DK_NONE);
+    for (int k = 0; k < no; k++) {
+        const mvp_det_op& op = g.ops[k];
+        const DetOpShape c = op_shape(g, k);
+        const DetKernel v = g.kernel[k] = select_det_kernel(c, op_fold(g, k), g.sw, cus);
+        MVP_REQUIRE(v != DK_NONE, "det op %d: no kernel serves kind %d, %dx%d, %d -> %d channels, ks %d stride %d", k,
+                    op.kind, c.h, c.w, c.cin, c.cout, c.ks, c.stride);
+        if (op.kind != MVP_DET_CONV) continue;
+        const mvp_tensor_desc& y = g.tensors[op.out.t];
+        MVP_REQUIRE(g.tensors[op.in.t].c % 8 == 0 && y.c % 4 == 0 && (op.res.t < 0 || g.tensors[op.res.t].c % 4 == 0),
+                    "det conv %d: pixel strides", k);
+        switch (v) {
+        case DK_BAND_8W:
+        case DK_BAND_4W:
+            MVP_REQUIRE(nmax * c.h / (c.w == 80 ? 4 : 8) < (1L << 24), "det band conv %d: too many bands", k);
+            break;
+        case DK_HALO_2ROW:
+        case DK_HALO:
+        case DK_HALO_LIVE3: {
+            const int tr = v == DK_HALO_2ROW ? 2 : DET_HALO_TR;
+            MVP_REQUIRE(nmax * ((c.h + tr - 1) / tr) * ((c.w + 63) / 64) < (1L << 31), "det conv %d: grid too large", k);
+            break;
+        }
+        case DK_FOLD_UP: {
+            const mvp_det_op& u = g.ops[g.fold_src[k]];
+            MVP_REQUIRE(c.h % 2 == 0 && c.w % 2 == 0 && u.out.c % 32 == 0 && u.out.c <= c.cin &&
+                            g.tensors[u.in.t].c % 8 == 0,
+                        "det conv %d: upsample fold shape", k);
+            [[fallthrough]];
+        }
+        case DK_FOLD_CA:
+        case DK_PERS_GEMM:
+        case DK_GEMM:
+            MVP_REQUIRE(det_gemm_blocks(nmax * y.h * y.w, det_cout_pad(c.cout)) < (1L << 31), "det conv %d: grid too large", k);
+            break;
+        default:
+            break;
         }
     }
 }
@@ -312,34 +402,34 @@ extern "C" int mvp_det_create(const mvp_tensor_desc* tensors, int n_tensors, con
         g->max_batch = max_batch;
         g->wb = w_dev;
         g->fb = f_dev;
+        g->sw = mvp::read_det_switches();
         mvp::validate(*g, w_elems, f_elems);
         mvp::plan_folds(*g);
+        mvp::select_kernels(*g, mvp::cu_count());
         mvp::plan(*g);
         hipError_t e = hipMalloc(&g->arena, g->arena_bytes);
         if (e != hipSuccess)
             mvp::fail(MVP_ERR_NOMEM, "mvp_det_create: arena of %lld bytes: %s", (long long)g->arena_bytes,
                       hipGetErrorString(e));
         MVP_HIP(hipMalloc(&g->ca_scratch, (size_t)max_batch * 17 * g->max_ca * sizeof(float)));  // launch_det_ca scratch
-        // conv weight images for the GEMM kernel (the blobs are not rewritten after create)
+        // the weight images the selected kernels read (the blobs are not rewritten after create)
         g->wimg.assign(g->ops.size(), nullptr);
         g->wband.assign(g->ops.size(), nullptr);
         for (size_t k = 0; k < g->ops.size(); k++) {
             const mvp_det_op& op = g->ops[k];
-            if (op.kind == MVP_DET_DWPW) {  // the pointwise weights' GEMM image
-                const int C = op.in.c;
-                MVP_HIP(hipMalloc(&g->wimg[k], (size_t)C * C * sizeof(uint16_t)));
-                mvp::det_pack_gemm_weights(w_dev + op.aux, g->wimg[k], C, C, nullptr);
+            const mvp::DetKernel v = g->kernel[k];
+            const size_t elems = (size_t)mvp::det_image_elems(v, mvp::op_shape(*g, (int)k));
+            if (!elems) continue;
+            const int npad = mvp::det_cout_pad(op.out.c);
+            if (v == mvp::DK_BAND_8W || v == mvp::DK_BAND_4W) {
+                MVP_HIP(hipMalloc(&g->wband[k], elems * sizeof(uint16_t)));
+                mvp::det_pack_band_weights(w_dev + op.w_off, g->wband[k], npad, op.in.c, nullptr);
                 continue;
             }
-            if (op.kind != MVP_DET_CONV) continue;
-            const int npad = mvp::det_cout_pad(op.out.c), K = op.ks * op.ks * op.in.c;
-            MVP_HIP(hipMalloc(&g->wimg[k], (size_t)npad * K * sizeof(uint16_t)));
-            mvp::det_pack_gemm_weights(w_dev + op.w_off, g->wimg[k], npad, K, nullptr);
-            const mvp_tensor_desc& xt = g->tensors[op.in.t];
-            if (mvp::det_band_eligible(xt.h, xt.w, op.in.c, npad, op.ks, op.stride)) {
-                MVP_HIP(hipMalloc(&g->wband[k], (size_t)mvp::det_band_rows(npad) * K * sizeof(uint16_t)));
-                mvp::det_pack_band_weights(w_dev + op.w_off, g->wband[k], npad, op.in.c, nullptr);
-            }
+            MVP_HIP(hipMalloc(&g->wimg[k], elems * sizeof(uint16_t)));
+            // dwpw: its pointwise weights (npad == cin)
+            mvp::det_pack_gemm_weights(w_dev + (op.kind == MVP_DET_DWPW ? op.aux : op.w_off), g->wimg[k], npad,
+                                       (int)(elems / npad), nullptr);
         }
         MVP_HIP(hipDeviceSynchronize());
     } catch (...) {
@@ -367,6 +457,23 @@ void run_ops(DetNet* g, const uint8_t* frames, int n, int h, int w, int begin, i
     static const float kStd[3] = {57.375f, 57.12f, 58.395f};
     // the letterbox folded into the stem (plan_folds) unless the caller wants the letterboxed image
     const bool lb_fused = begin == 0 && g->lb_folded && !letterboxed;
+    // a conv as its kernel family takes it
+    auto conv_params = [&](int k) {
+        const mvp_det_op& op = g->ops[k];
+        const mvp_tensor_desc &x = T(op.in.t), &y = T(op.out.t);
+        const int npad = det_cout_pad(op.out.c), bn = det_conv_bn(npad);
+        const bool res = op.res.t >= 0;
+        GParams p{vp(op.in), g->wb + op.w_off, g->fb + op.b_off, res ? vp(op.res) : nullptr, vp(op.out),
+                  conv_zero_region(), (long)n * y.h * y.w, op.in.c, op.out.c, npad, x.c, y.c, res ? T(op.res.t).c : 0,
+                  op.act, (npad + bn - 1) / bn, g->sw.xcd, x.h, x.w, y.h, y.w, g->wimg[k]};
+        if (g->kernel[k] == DK_FOLD_UP) {
+            const mvp_det_op& u = g->ops[g->fold_src[k]];
+            p.up = vp(u.in), p.up_s = T(u.in.t).c, p.up_c = u.out.c;
+        } else if (g->kernel[k] == DK_FOLD_CA) {
+            p.ca = det_ca_scales(g->ca_scratch, n, op.in.c);
+        }
+        return p;
+    };
     if (begin == 0 && !lb_fused) launch_det_letterbox(frames, n, h, w, g->size, kMean, kStd, base(g->input), s);
     for (int k = begin; k < end; k++) {
         const mvp_det_op& op = g->ops[k];
@@ -379,23 +486,16 @@ void run_ops(DetNet* g, const uint8_t* frames, int n, int h, int w, int begin, i
                     launch_det_stem(vp(op.in), g->fb + op.w_off, g->fb + op.b_off, vp(op.out), n, g->size, op.act, s);
                 break;
             case MVP_DET_CONV: {
-                const mvp_tensor_desc& x = T(op.in.t);
-                DetConvFold fold;
-                if (g->fold_src[k] >= 0) {
-                    const mvp_det_op& u = g->ops[g->fold_src[k]];
-                    if (u.kind == MVP_DET_UP2) {
-                        fold.up = vp(u.in);
-                        fold.up_s = T(u.in.t).c;
-                        fold.up_c = u.out.c;
-                    } else {
-                        fold.ca = det_ca_scales(g->ca_scratch, n, op.in.c);
-                    }
+                const GParams p = conv_params(k);
+                switch (g->kernel[k]) {
+                    case DK_BAND_8W:
+                    case DK_BAND_4W: det_launch_band(p, n, g->wband[k], g->kernel[k] == DK_BAND_4W, s); break;
+                    case DK_FOLD_UP:
+                    case DK_FOLD_CA: det_launch_fold(p, g->kernel[k], g->sw.pers_occ, s); break;
+                    case DK_PERS_GEMM: det_launch_pers(p, op.ks, op.stride, g->sw.pers_occ, s); break;
+                    case DK_GEMM: det_launch_gemm(p, op.ks, op.stride, s); break;
+                    default: det_launch_halo(p, n, g->kernel[k], s); break;
                 }
-                launch_det_conv_gemm(vp(op.in), x.c, g->wb + op.w_off, g->fb + op.b_off,
-                                     op.res.t >= 0 ? vp(op.res) : nullptr, op.res.t >= 0 ? T(op.res.t).c : 0,
-                                     vp(op.out), T(op.out.t).c, n, x.h, x.w, op.in.c, op.out.c, op.ks, op.stride,
-                                     op.act, s, g->wimg[k], g->wband[k], (int)op.aux,
-                                     g->fold_src[k] >= 0 ? &fold : nullptr);
                 break;
             }
             case MVP_DET_DW: {
@@ -432,7 +532,7 @@ void run_ops(DetNet* g, const uint8_t* frames, int n, int h, int w, int begin, i
             case MVP_DET_HEAD: {
                 const mvp_tensor_desc& x = T(op.in.t);
                 launch_det_head(vp(op.in), x.c, op.in.c / 2, g->fb + op.w_off, g->fb + op.b_off, cand, n, x.h, x.w,
-                                op.stride, g->size, g->n_priors, (int)op.aux, s);
+                                op.stride, g->size, g->n_priors, (int)op.aux, g->kernel[k] == DK_HEAD_DIRECT, s);
                 break;
             }
         }
@@ -486,6 +586,30 @@ extern "C" int mvp_det_folded_ops(void* handle, int* folded_out, int n_ops) {
     if (g->lb_folded && n_ops > 0) folded_out[0] = 2;
     MVP_ABI_END
 }
+
+extern "C" int mvp_det_kernels(void* handle, int* kernels_out, int max_records, int* n_records) {
+    MVP_ABI_BEGIN
+    DetNet* g = static_cast<DetNet*>(handle);
+    MVP_REQUIRE(g != nullptr && n_records != nullptr && (kernels_out != nullptr || max_records == 0),
+                "mvp_det_kernels: NULL argument");
+    std::vector<int> ks;
+    if (!g->lb_folded) ks.push_back(mvp::DK_LETTERBOX);
+    for (size_t k = 0; k < g->ops.size(); k++) {
+        if (g->ops[k].kind == MVP_DET_UP2 && g->folded[k]) continue;  // runs inside its consumer
+        ks.push_back(g->kernel[k]);
+        if (g->ops[k].kind != MVP_DET_CA) continue;
+        ks.push_back(mvp::DK_CA_FC);
+        if (!g->folded[k]) ks.push_back(mvp::DK_CA_SCALE);
+    }
+    ks.push_back(mvp::DK_SELECT);
+    *n_records = (int)ks.size();
+    MVP_REQUIRE((int)ks.size() <= max_records || max_records == 0, "mvp_det_kernels: %zu launches, room for %d", ks.size(),
+                max_records);
+    if (max_records) std::copy(ks.begin(), ks.end(), kernels_out);
+    MVP_ABI_END
+}
+
+extern "C" const char* mvp_det_kernel_name(int kernel) { return mvp::det_kernel_name(kernel); }
 
 extern "C" int mvp_det_tensor_copy(void* handle, int t, int n, void* buf, int to_arena, void* stream) {
     MVP_ABI_BEGIN

@@ -89,6 +89,8 @@ SIGNATURES = {
     "mvp_det_run_ops": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "mvp_det_tensor_copy": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "mvp_det_folded_ops": (c_int, [c_void_p, c_void_p, c_int]),
+    "mvp_det_kernels": (c_int, [c_void_p, c_void_p, c_int, P(c_int)]),
+    "mvp_det_kernel_name": (c_char_p, [c_int]),
     "mvp_det_destroy": (c_int, [c_void_p]),
     "mvp_sgd_workspace_floats": (c_int, [c_int, c_int, c_int, c_int, P(c_int64)]),
     # mvp_sgd_params struct pointer declared in mvpose/refine.py

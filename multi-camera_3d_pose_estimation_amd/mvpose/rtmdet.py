@@ -570,6 +570,22 @@ class RTMDetector:
         call("mvp_det_folded_ops", self._h, out, len(self.spec.ops))
         return list(out)
 
+    def launch_kernels(self) -> list[str]:
+        """The kernel variant of every launch of one forward, in launch order (mvp_det_kernels):
+        chosen when the detector was created, from the MVPOSE_DET_* switches as they were then."""
+        n = ctypes.c_int()
+        call("mvp_det_kernels", self._h, None, 0, ctypes.byref(n))
+        ids = (ctypes.c_int * n.value)()
+        call("mvp_det_kernels", self._h, ids, n.value, ctypes.byref(n))
+        return [_lib.lib.mvp_det_kernel_name(k).decode() for k in ids]
+
+    def set_tensor(self, t: int, x: torch.Tensor) -> None:
+        """Overwrite arena tensor t's first len(x) images with x, (n, h, w, c) bf16."""
+        h, w, c, _ = self.spec.tensors[t]
+        assert x.dtype == torch.bfloat16 and tuple(x.shape[1:]) == (h, w, c) and x.is_contiguous(), x.shape
+        call("mvp_det_tensor_copy", self._h, t, x.shape[0], ctypes.c_void_p(x.data_ptr()), 1,
+             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+
     def tensor(self, t: int, n: int) -> torch.Tensor:
         """Copy of arena tensor t (first n images) as (n, h, w, c) bf16."""
         h, w, c, _ = self.spec.tensors[t]

@@ -307,9 +307,17 @@ def test_band_conv_vs_gemm(sd, monkeypatch):
     band-halo kernel (det_conv_band_kernel, the default): each one, on the forward's own input,
     against the im2col GEMM kernel (MVPOSE_DET_BAND=0).  K order (chunk, tap, channel) vs (tap,
     chunk, channel): equal to f32 rounding, so the bf16 outputs agree to within a bf16 ulp where
-    the f32 sums straddle a rounding boundary (3 frames: the bands' XCD groups are uneven)."""
+    the f32 sums straddle a rounding boundary (3 frames: the bands' XCD groups are uneven).  A
+    detector chooses its kernels when it is created, so there is one per MVPOSE_DET_BAND setting;
+    the other two run each conv alone on a copy of the default detector's input (and residual)."""
     n = 3
-    det = D.RTMDetector(sd, max_batch=n, size=640)
+    monkeypatch.setenv("MVPOSE_DET_FOLD", "1")
+    dets = {}
+    for band in ("0", "1", "4"):  # the GEMM kernel, the band kernel (8 waves), its 4-wave form
+        monkeypatch.setenv("MVPOSE_DET_BAND", band)
+        dets[band] = D.RTMDetector(sd, max_batch=n, size=640)
+    monkeypatch.delenv("MVPOSE_DET_BAND")
+    det = dets["1"]
     spec = det.spec
     frames = torch.from_numpy(_frames(n, 720, 1280, seed=9)).cuda()
     det.run_ops(frames, 0, len(spec.ops))
@@ -322,11 +330,13 @@ def test_band_conv_vs_gemm(sd, monkeypatch):
         op = spec.ops[k]
         lo, hi = op.out.coff, op.out.coff + op.out.c
         outs = {}
-        for band in ("0", "1", "4"):  # the GEMM kernel, the band kernel (8 waves), its 4-wave form
-            monkeypatch.setenv("MVPOSE_DET_BAND", band)
-            det.run_ops(frames, k, k + 1)
+        for band, d in dets.items():
+            if d is not det:
+                for t in {op.in_.t, op.res.t} - {-1}:
+                    d.set_tensor(t, det.tensor(t, n))
+            d.run_ops(frames, k, k + 1)
             torch.cuda.synchronize()
-            outs[band] = det.tensor(op.out.t, n).float().cpu()[..., lo:hi]
+            outs[band] = d.tensor(op.out.t, n).float().cpu()[..., lo:hi]
         # each output's MFMA sequence is the same in both band forms: bit-identical
         assert torch.equal(outs["1"], outs["4"]), spec.names[k]
         a, b = outs["1"], outs["0"]
@@ -337,7 +347,8 @@ def test_band_conv_vs_gemm(sd, monkeypatch):
         n_bad = int((diff > b.abs() * 2 ** -7 + 2 ** -9 * scale).sum())
         frac_diff = float((diff > 0).float().mean())
         assert finite and n_bad == 0 and frac_diff < 0.05, (spec.names[k], n_bad, float(diff.max()), frac_diff)
-    det.close()
+    for d in dets.values():
+        d.close()
 
 
 @pytest.mark.parametrize("size,n", [(128, 3), (640, 2)])

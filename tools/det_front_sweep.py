@@ -13,7 +13,6 @@ from mvpose import rtmdet as D  # noqa: E402
 
 batch = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-os.environ["MVPOSE_DET_MB"] = "0"
 det = D.RTMDetector(seed=0, max_batch=batch)
 g = torch.Generator(device="cuda").manual_seed(0)
 frames = torch.randint(0, 256, (batch, 720, 1280, 3), dtype=torch.uint8, device="cuda", generator=g)

@@ -4,6 +4,12 @@
 // (switch: a Switches field name, or s2_tile=N) and prints for each
 //     <kernel below one crop per CU> <kernel from there on> <kernel at this batch> <weight image elements>
 // (kernel_name(), "tblock64_kernel:tiles" for tblock64_kernel's strided form, "none" for K_NONE).
+// A line that starts with "det" asks the person detector's selection (csrc/det_select.h) instead:
+//     det kind h w cin cout ks stride live res fold cus  [switch=value ...]
+// (kind: MVP_DET_*; fold: DetFold; switch: a DetSwitches field, e.g. band=4 pers=0 halo_rows2=1)
+// and prints
+//     <variant> <weight image elements>
+// (det_kernel_name(), "none" for DK_NONE).
 // tests/test_kernel_select.py builds it with the host compiler and holds the expected answers.
 //   c++ -std=c++17 -O1 -Imulti-camera_3d_pose_estimation_amd/csrc tools/kernel_select_check.cpp -o kernel_select_check
 #include <cstdio>
@@ -13,13 +19,51 @@
 #include <sstream>
 #include <string>
 
+#include "det_select.h"
 #include "kernel_select.h"
+
+// one "det" query (the stream stands after the word); false: malformed
+static bool det_query(std::istringstream& in) {
+    using namespace mvp;
+    DetOpShape c;
+    int fold, cus;
+    if (!(in >> c.kind >> c.h >> c.w >> c.cin >> c.cout >> c.ks >> c.stride >> c.live >> c.res >> fold >> cus)) return false;
+    DetSwitches sw;
+    for (std::string w; in >> w;) {
+        const size_t eq = w.find('=');
+        if (eq == std::string::npos) return false;
+        const std::string name = w.substr(0, eq);
+        const int v = atoi(w.c_str() + eq + 1);
+        if (name == "xcd") sw.xcd = v;
+        else if (name == "band") sw.band = v;
+        else if (name == "pers") sw.pers = v;
+        else if (name == "pers_occ") sw.pers_occ = v;
+        else if (name == "fold") sw.fold = v;
+        else if (name == "halo_pers") sw.halo_pers = v;
+        else if (name == "halo_rows2") sw.halo_rows2 = v;
+        else if (name == "live") sw.live = v;
+        else if (name == "head_direct") sw.head_direct = v;
+        else return false;
+    }
+    const DetKernel k = select_det_kernel(c, (DetFold)fold, sw, cus);
+    printf("%s %ld\n", k == DK_NONE ? "none" : det_kernel_name(k), det_image_elems(k, c));
+    return true;
+}
 
 int main() {
     using namespace mvp;
     std::string line;
     while (std::getline(std::cin, line)) {
         std::istringstream in(line);
+        if (line.rfind("det ", 0) == 0) {
+            std::string word;
+            in >> word;
+            if (!det_query(in)) {
+                fprintf(stderr, "bad detector query: %s\n", line.c_str());
+                return 2;
+            }
+            continue;
+        }
         int route, batch, cus, has_image;
         LaunchShape c;
         if (!(in >> route >> c.cin >> c.cout >> c.h >> c.w >> c.ks >> c.stride >> c.relu >> c.res >> c.f32_out >> c.cat >>
