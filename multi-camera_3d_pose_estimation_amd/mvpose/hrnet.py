@@ -279,6 +279,26 @@ class GraphSpec:
         return w, f
 
 
+def fuse_layer(g: GraphSpec, sd, p: str, i: int, xs, relu: bool = True) -> int:
+    """Fuse layer i of the HRModule `p` on its branch outputs xs (mmpose's fuse_layers[i]): branch
+    j > i through a 1x1 projection (BN, no ReLU) and a nearest upsample by 2 ** (j - i), branch
+    j < i through i - j 3x3/s2 convs (BN; ReLU on all but the last), summed in branch order."""
+    terms = []
+    for j in range(len(xs)):
+        if j == i:
+            terms.append((xs[j], 1))
+        elif j > i:
+            t = g.conv(sd, f"{p}.fuse_layers.{i}.{j}.0", f"{p}.fuse_layers.{i}.{j}.1", xs[j], 1, False)
+            terms.append((t, 2 ** (j - i)))
+        else:
+            t = xs[j]
+            for k in range(i - j):
+                t = g.conv(sd, f"{p}.fuse_layers.{i}.{j}.{k}.0", f"{p}.fuse_layers.{i}.{j}.{k}.1", t, 2,
+                           k != i - j - 1)
+            terms.append((t, 1))
+    return g.fuse(terms, relu)
+
+
 def build_hrnet_w32(sd, micro_batch=None) -> tuple[GraphSpec, int, int]:
     """Walk mmpose's HRNet-W32 + HeatmapHead forward order; returns (spec, input id, output id)."""
     mb = micro_batch_config() if micro_batch is None else micro_batch
@@ -321,20 +341,7 @@ def build_hrnet_w32(sd, micro_batch=None) -> tuple[GraphSpec, int, int]:
             n_out = 1 if last else len(chans)
             outs = []
             for i in range(n_out):
-                terms = []
-                for j in range(len(chans)):
-                    if j == i:
-                        terms.append((xs[j], 1))
-                    elif j > i:
-                        t = g.conv(sd, f"{p}.fuse_layers.{i}.{j}.0", f"{p}.fuse_layers.{i}.{j}.1", xs[j], 1, False)
-                        terms.append((t, 2 ** (j - i)))
-                    else:
-                        t = xs[j]
-                        for k in range(i - j):
-                            t = g.conv(sd, f"{p}.fuse_layers.{i}.{j}.{k}.0", f"{p}.fuse_layers.{i}.{j}.{k}.1", t, 2,
-                                       k != i - j - 1)
-                        terms.append((t, 1))
-                outs.append(g.fuse(terms))
+                outs.append(fuse_layer(g, sd, p, i, xs))
             xs = outs
         ys = xs
         pre = list(chans)
@@ -342,94 +349,103 @@ def build_hrnet_w32(sd, micro_batch=None) -> tuple[GraphSpec, int, int]:
     return g, x_in, out
 
 
-def basic_block_spec(c: int, h: int, w: int, seed: int = 0, n_blocks: int = 1):
+def _given(seeded, sd):
+    """The state dict a spec helper folds: its own seeded one, or `sd` (same keys and shapes)
+    in its place, so that a test can rewrite the weights and build the same graph from them."""
+    if sd is None:
+        return seeded
+    if set(sd) != set(seeded):
+        raise ValueError(f"sd: keys differ from the spec's: {sorted(set(sd) ^ set(seeded))}")
+    for k, v in seeded.items():
+        if tuple(sd[k].shape) != tuple(v.shape):
+            raise ValueError(f"sd[{k!r}]: shape {tuple(sd[k].shape)}, expected {tuple(v.shape)}")
+    return dict(sd)
+
+
+def _seed_conv_bn(sd, gen, conv, bn, co, ci, k):
+    """He-normal conv weight and a BatchNorm with randomised affine and running statistics."""
+    sd[f"{conv}.weight"] = torch.randn((co, ci, k, k), generator=gen) * (2.0 / (k * k * ci)) ** 0.5
+    sd[f"{bn}.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
+    sd[f"{bn}.bias"] = 0.1 * torch.randn((co,), generator=gen)
+    sd[f"{bn}.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
+    sd[f"{bn}.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
+
+
+def basic_block_spec(c: int, h: int, w: int, seed: int = 0, n_blocks: int = 1, sd=None):
     """A chain of n_blocks HRNet BasicBlocks (conv3x3+BN+ReLU, conv3x3+BN, +x, ReLU)
     on one c-channel h x w plane, for kernel tests and per-layer benchmarks.
-    Returns (spec, input id, output id, state dict)."""
+    Returns (spec, input id, output id, state dict); `sd` replaces the seeded weights (same
+    keys and shapes), as on every spec helper below."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
+    seeded = {}
+    for k in range(n_blocks):
+        for j in (1, 2):
+            _seed_conv_bn(seeded, gen, f"b{k}.conv{j}", f"b{k}.bn{j}", c, c, 3)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(h, w, c)
     y = x
     for k in range(n_blocks):
-        for j in (1, 2):
-            sd[f"b{k}.conv{j}.weight"] = torch.randn((c, c, 3, 3), generator=gen) * (2.0 / (9 * c)) ** 0.5
-            sd[f"b{k}.bn{j}.weight"] = 1.0 + 0.1 * torch.randn((c,), generator=gen)
-            sd[f"b{k}.bn{j}.bias"] = 0.1 * torch.randn((c,), generator=gen)
-            sd[f"b{k}.bn{j}.running_mean"] = 0.1 * torch.randn((c,), generator=gen)
-            sd[f"b{k}.bn{j}.running_var"] = 1.0 + 0.2 * torch.rand((c,), generator=gen)
         t = g.conv(sd, f"b{k}.conv1", f"b{k}.bn1", y, 1, True)
         y = g.conv(sd, f"b{k}.conv2", f"b{k}.bn2", t, 1, True, res=y)
     return g, x, y, sd
 
 
-def projection_spec(cin: int, cout: int, h: int, w: int, k: int = 1, seed: int = 0):
+def projection_spec(cin: int, cout: int, h: int, w: int, k: int = 1, seed: int = 0, sd=None):
     """Two k x k convs cin -> cout on one h x w plane: t = conv_a(x) (BN, no ReLU) and
     y = relu(conv_b(x) + t) (the Bottleneck conv3 + downsample pattern), for kernel
     tests.  Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
+    seeded = {}
+    for j in ("a", "b"):
+        _seed_conv_bn(seeded, gen, j, f"{j}bn", cout, cin, k)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(h, w, cin)
-    for j in ("a", "b"):
-        sd[f"{j}.weight"] = torch.randn((cout, cin, k, k), generator=gen) * (2.0 / (k * k * cin)) ** 0.5
-        sd[f"{j}bn.weight"] = 1.0 + 0.1 * torch.randn((cout,), generator=gen)
-        sd[f"{j}bn.bias"] = 0.1 * torch.randn((cout,), generator=gen)
-        sd[f"{j}bn.running_mean"] = 0.1 * torch.randn((cout,), generator=gen)
-        sd[f"{j}bn.running_var"] = 1.0 + 0.2 * torch.rand((cout,), generator=gen)
     t = g.conv(sd, "a", "abn", x, 1, False)
     y = g.conv(sd, "b", "bbn", x, 1, True, res=t)
     return g, x, y, sd
 
 
-def join_spec(h: int, w: int, seed: int = 0, cat: bool = False):
+def join_spec(h: int, w: int, seed: int = 0, cat: bool = False, sd=None):
     """Layer1 Bottleneck join on an h x w plane: r = conv_r(x) (64 -> 256; ReLU unless
     `cat`, when it is the downsample that cat-fusion folds into conv_a), y = relu(conv_a(x)
     + r) (64 -> 256, the Bottleneck conv3) and out = relu(conv_b(y)) (256 -> 64, the next
     Bottleneck's conv1) — the pattern the graph's pair-fusion pass runs as one launch.
     Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
+    seeded = {}
+    for j, (co, ci) in (("r", (256, 64)), ("a", (256, 64)), ("b", (64, 256))):
+        _seed_conv_bn(seeded, gen, j, f"{j}bn", co, ci, 1)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(h, w, 64)
-    for j, (co, ci) in (("r", (256, 64)), ("a", (256, 64)), ("b", (64, 256))):
-        sd[f"{j}.weight"] = torch.randn((co, ci, 1, 1), generator=gen) * (2.0 / ci) ** 0.5
-        sd[f"{j}bn.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.bias"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
     r = g.conv(sd, "r", "rbn", x, 1, not cat)
     y = g.conv(sd, "a", "abn", x, 1, True, res=r)
     out = g.conv(sd, "b", "bbn", y, 1, True)
     return g, x, out, sd
 
 
-def bottleneck_spec(seed: int = 0, n_blocks: int = 4, lead: bool = True):
+def bottleneck_spec(seed: int = 0, n_blocks: int = 4, lead: bool = True, sd=None):
     """HRNet-W32 layer1 on the 64x48 plane: n_blocks Bottlenecks (1x1 -> 64 + ReLU, 3x3 64 -> 64
     + ReLU, 1x1 -> 256 + identity + ReLU).  lead=True: the first block takes a 64-ch input with
     its 1x1 downsample as the identity (HRNet's layer1.0, whose conv3 the graph cat-fuses), the
     rest run on 256 ch; lead=False: every block on a 256-ch input.  For kernel tests.
     Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
-
-    def mk(name, co, ci, k):
-        sd[f"{name}.weight"] = torch.randn((co, ci, k, k), generator=gen) * (2.0 / (k * k * ci)) ** 0.5
-        sd[f"{name}bn.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{name}bn.bias"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{name}bn.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{name}bn.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
-
+    seeded = {}
+    for b in range(n_blocks):
+        first = lead and b == 0
+        _seed_conv_bn(seeded, gen, f"b{b}.conv1", f"b{b}.conv1bn", 64, 64 if first else 256, 1)
+        _seed_conv_bn(seeded, gen, f"b{b}.conv2", f"b{b}.conv2bn", 64, 64, 3)
+        _seed_conv_bn(seeded, gen, f"b{b}.conv3", f"b{b}.conv3bn", 256, 64, 1)
+        if first:
+            _seed_conv_bn(seeded, gen, f"b{b}.ds", f"b{b}.dsbn", 256, 64, 1)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x_in = x = g.tensor(64, 48, 64 if lead else 256)
     for b in range(n_blocks):
         first = lead and b == 0
-        cin = 64 if first else 256
-        mk(f"b{b}.conv1", 64, cin, 1)
-        mk(f"b{b}.conv2", 64, 64, 3)
-        mk(f"b{b}.conv3", 256, 64, 1)
-        if first:
-            mk(f"b{b}.ds", 256, 64, 1)
         idn = g.conv(sd, f"b{b}.ds", f"b{b}.dsbn", x, 1, False) if first else x
         y = g.conv(sd, f"b{b}.conv1", f"b{b}.conv1bn", x, 1, True)
         y = g.conv(sd, f"b{b}.conv2", f"b{b}.conv2bn", y, 1, True)
@@ -445,21 +461,18 @@ def layer1_transition_spec(seed: int = 0, output: int = 0):
     g, x, y, sd = bottleneck_spec(seed=seed, n_blocks=4, lead=True)
     gen = torch.Generator().manual_seed(seed + 1)
     for j, co in (("t0", 32), ("t1", 64)):
-        sd[f"{j}.weight"] = torch.randn((co, 256, 3, 3), generator=gen) * (2.0 / (9 * 256)) ** 0.5
-        sd[f"{j}bn.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.bias"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
+        _seed_conv_bn(sd, gen, j, f"{j}bn", co, 256, 3)
     t0 = g.conv(sd, "t0", "t0bn", y, 1, True)
     t1 = g.conv(sd, "t1", "t1bn", y, 2, True)
     return g, x, (t0, t1)[output], sd
 
 
-def stem_spec(seed: int = 0):
+def stem_spec(seed: int = 0, sd=None):
     """HRNet's stem on a 256x192 crop: conv1 (3x3/s2 4 -> 64) and conv2 (3x3/s2 64 -> 64),
     BN + ReLU each (the pattern the graph's stem-fusion pass runs as one launch), for
     kernel tests.  Returns (spec, input id, output id, state dict)."""
-    sd = {k: v for k, v in random_state_dict(seed).items() if k.startswith(("backbone.conv", "backbone.bn"))}
+    seeded = {k: v for k, v in random_state_dict(seed).items() if k.startswith(("backbone.conv", "backbone.bn"))}
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(INPUT_HW[0], INPUT_HW[1], 4)
     y = g.stem(sd, "backbone.conv1", "backbone.bn1", x)
@@ -467,19 +480,16 @@ def stem_spec(seed: int = 0):
     return g, x, y, sd
 
 
-def transition_spec(seed: int = 0, output: int = 0):
+def transition_spec(seed: int = 0, output: int = 0, sd=None):
     """HRNet-W32 transition1 on the layer1 output (256 ch @ 64x48): t0 = 3x3/s1 -> 32 ch and
     t1 = 3x3/s2 -> 64 ch, both BN + ReLU (the pair the graph's transition-fusion pass runs
     as one launch); the graph output is t0 (output=0) or t1 (output=1).  For kernel tests.
     Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
+    seeded = {}
     for j, co in (("t0", 32), ("t1", 64)):
-        sd[f"{j}.weight"] = torch.randn((co, 256, 3, 3), generator=gen) * (2.0 / (9 * 256)) ** 0.5
-        sd[f"{j}bn.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.bias"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
+        _seed_conv_bn(seeded, gen, j, f"{j}bn", co, 256, 3)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(64, 48, 256)
     t0 = g.conv(sd, "t0", "t0bn", x, 1, True)
@@ -490,38 +500,78 @@ def transition_spec(seed: int = 0, output: int = 0):
 SIBLINGS = (("s1", 64, False), ("s2", 32, True), ("s3", 32, True))
 
 
-def sibling_spec(seed: int = 0, output: int = 0, n: int = 3):
+def sibling_spec(seed: int = 0, output: int = 0, n: int = 3, sd=None):
     """A stage-4 HRModule fuse layer's 3x3/s2 convs on the branch-0 tensor (32 ch @ 64x48):
     s1 -> 64 ch (BN, no ReLU), s2 / s3 -> 32 ch (BN + ReLU) — the first n of them, the
     siblings the graph's sibling-fusion pass runs as one launch; the graph output is
     sibling `output`.  For kernel tests.  Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {}
+    seeded = {}
     for j, co, _ in SIBLINGS[:n]:
-        sd[f"{j}.weight"] = torch.randn((co, 32, 3, 3), generator=gen) * (2.0 / (9 * 32)) ** 0.5
-        sd[f"{j}bn.weight"] = 1.0 + 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.bias"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_mean"] = 0.1 * torch.randn((co,), generator=gen)
-        sd[f"{j}bn.running_var"] = 1.0 + 0.2 * torch.rand((co,), generator=gen)
+        _seed_conv_bn(seeded, gen, j, f"{j}bn", co, 32, 3)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(64, 48, 32)
     outs = [g.conv(sd, j, j + "bn", x, 2, relu) for j, _, relu in SIBLINGS[:n]]
     return g, x, outs[output], sd
 
 
-def conv_spec(cin: int, cout: int, h: int, w: int, k: int = 3, stride: int = 1, relu: bool = True, seed: int = 0):
+def conv_spec(cin: int, cout: int, h: int, w: int, k: int = 3, stride: int = 1, relu: bool = True, seed: int = 0,
+              sd=None):
     """One k x k conv (+ folded BN, optional ReLU) cin -> cout on an h x w plane, for
     kernel tests and per-conv benchmarks.  Returns (spec, input id, output id, state dict)."""
     gen = torch.Generator().manual_seed(seed)
-    sd = {"c.weight": torch.randn((cout, cin, k, k), generator=gen) * (2.0 / (k * k * cin)) ** 0.5,
-          "bn.weight": 1.0 + 0.1 * torch.randn((cout,), generator=gen),
-          "bn.bias": 0.1 * torch.randn((cout,), generator=gen),
-          "bn.running_mean": 0.1 * torch.randn((cout,), generator=gen),
-          "bn.running_var": 1.0 + 0.2 * torch.rand((cout,), generator=gen)}
+    seeded = {}
+    _seed_conv_bn(seeded, gen, "c", "bn", cout, cin, k)
+    sd = _given(seeded, sd)
     g = GraphSpec()
     x = g.tensor(h, w, cin)
     y = g.conv(sd, "c", "bn", x, stride, relu)
     return g, x, y, sd
+
+
+FUSE_CHANNELS = STAGES[-1][1]
+
+
+def fuse_layer_spec(n_branches: int, output: int, head: bool = False, relu: bool = True, lead_relu: bool = True,
+                    sd=None, seed: int = 0):
+    """Fuse layer `output` of an HRModule with n_branches branches (fuse_layer, the wiring
+    build_hrnet_w32 uses), on branch tensors made from the one 32-ch 64x48 input x: b0 = x and
+    b_j = 3x3/s2 conv of b_{j-1} to FUSE_CHANNELS[j] channels (BN; ReLU if lead_relu), keys
+    lead.{j}.0 / lead.{j}.1.  The layer's keys are mod.fuse_layers.{output}.{j}... as in mmpose.
+    head=True (output 0 only): the 1x1 32 -> 17 heatmap head (head.final_layer, bias, f32 NCHW
+    output) follows, the pattern the graph's head-fusion pass runs as one launch.  For kernel
+    tests.  Returns (spec, input id, output id, state dict)."""
+    chans = FUSE_CHANNELS[:n_branches]
+    if not (2 <= n_branches <= len(FUSE_CHANNELS) and 0 <= output < n_branches):
+        raise ValueError(f"fuse_layer_spec: n_branches={n_branches}, output={output}")
+    if head and output != 0:
+        raise ValueError("fuse_layer_spec: the head reads fuse layer 0")
+    gen = torch.Generator().manual_seed(seed)
+    seeded = {}
+    for j in range(1, n_branches):
+        _seed_conv_bn(seeded, gen, f"lead.{j}.0", f"lead.{j}.1", chans[j], chans[j - 1], 3)
+    i = output
+    for j in range(n_branches):
+        q = f"mod.fuse_layers.{i}.{j}"
+        if j > i:
+            _seed_conv_bn(seeded, gen, f"{q}.0", f"{q}.1", chans[i], chans[j], 1)
+        for k in range(i - j):
+            _seed_conv_bn(seeded, gen, f"{q}.{k}.0", f"{q}.{k}.1", chans[i] if k == i - j - 1 else chans[j], chans[j], 3)
+    if head:
+        seeded["head.final_layer.weight"] = torch.randn((N_JOINTS, 32, 1, 1), generator=gen) * (2.0 / 32) ** 0.5
+        seeded["head.final_layer.bias"] = 0.1 * torch.randn((N_JOINTS,), generator=gen)
+    sd = _given(seeded, sd)
+    g = GraphSpec()
+    x = g.tensor(HEATMAP_HW[0], HEATMAP_HW[1], chans[0])
+    xs = [x]
+    for j in range(1, n_branches):
+        xs.append(g.conv(sd, f"lead.{j}.0", f"lead.{j}.1", xs[-1], 2, lead_relu))
+    y = fuse_layer(g, sd, "mod", i, xs, relu)
+    if head:
+        y = g.conv(sd, "head.final_layer", None, y, 1, False, out_dtype=DT_F32)
+    return g, x, y, sd
+
 
 
 class ConvGraph:
