@@ -929,7 +929,8 @@ int mvp_bundle_adjust(const float* kpts_dev, int64_t n_points, int V, const doub
  * chunk = 0 or 4..4096.  Argument errors return MVP_ERR_ARG before any device work.
  * Out of scope: a posterior covariance of the trajectory (it needs the selected inverse of A, not
  * a solve); sub-frame time offsets between the cameras (mvp_epipolar_lag_cost finds whole frames);
- * coupling between chains such as bone lengths (chains stay independent).
+ * coupling between chains such as bone lengths (chains stay independent here; mvp_skeleton_fit
+ * below couples them).
  * ------------------------------------------------------------------------- */
 int mvp_trajectory_fit_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
 int mvp_trajectory_fit_system(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
@@ -943,6 +944,104 @@ int mvp_trajectory_fit(const float* kpts_dev, int T, int P, int V, const double*
                        double lambda_smooth, int max_iter, double tol, int chunk, void* workspace_dev,
                        int64_t workspace_bytes, float* out_xyz_dev, float* out_resid_dev, uint8_t* out_nviews_dev,
                        double* out_cost_dev, uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The trajectory fit with a person's joints coupled by bone lengths: the third of the costs the
+ * reference refines against (reprojection, smoothness, body-part lengths; mvp_sgd_refine has all
+ * three in f32 under Adam, mvp_trajectory_fit the first two).  A known upper-arm length pins the
+ * depth of an elbow that one camera has lost on the ray of the camera that still sees it, which a
+ * stiffer smoothness prior does not do.
+ *
+ * Every input of mvp_trajectory_fit with the same meaning, and P = G·J: chain p = g·J + j is joint
+ * j of person (group) g, 1 <= J <= 255.  seg_host [n_seg][2] int, 0 <= n_seg <= 64: segment s joins
+ * joints (a, b), a != b, both < J, no unordered pair twice.  seg_len_dev [G][n_seg] float32: one
+ * set of lengths L per person, in world units; a length that is not finite or not > 0 makes that
+ * segment dead for that person.  lambda_bone = β, finite and >= 0, in pixel-weight units per
+ * (world unit)²: with unit weights β = (σ_px / σ_L)², σ_L the tolerance of a length.
+ *   Valid chain: mvp_trajectory_fit's rule without its last clause: the seed is finite in every
+ *     frame; every used view has P_z > 0 at the seed; at least 2 frames have at least 2 used views.
+ *     An invalid chain takes no part: it returns its seed's bits with chain status 0x80, and the
+ *     segments that end at it are dead.
+ *   Valid group: at least one valid chain, and the group's cost at the seed is finite.  Every chain
+ *     of an invalid group is returned as it came (chain status 0x80, NaN resid), the group's status
+ *     is 0x80 and its costs are NaN.
+ *   Cost per group, over its valid chains and live segments, r = |X_{t,b} - X_{t,a}|,
+ *     n = (X_{t,b} - X_{t,a}) / r:
+ *       f_g = Σ_chains (Σ_t Σ_used rho + ½ λ Σ_t |second difference|²) + ½ β Σ_t Σ_s (r - L_{g,s})²
+ *     and +inf when a used view of a valid chain has P_z <= 0.  A term with r == 0 costs ½ β L² and
+ *     contributes no gradient and no curvature.
+ *   Linearisation: per chain mvp_trajectory_fit's H~_t and g~_t, plus for every live segment that
+ *     ends at the chain's joint
+ *       to g~_t at end b: β·(r - L)·n, at end a its negative (the exact gradient);
+ *       to H~_t at both ends: 2β·[n nᵀ + max(0, 1 - L/r)·(I - n nᵀ)].
+ *     That block is twice the positive-semidefinite part of the term's own Hessian; the factor 2
+ *     bounds the a-b cross block, which is dropped.  So the chains stay independent inside a
+ *     trial, and the coupling acts from trial to trial.
+ *   Trial, per group with one mu_g: every valid chain solves (A_p + mu_g·diag A_p)·d_p = -G_p by
+ *     mvp_trajectory_fit's solver and forms X_p + d_p.  A pivot that is not > 0 in any chain of the
+ *     group rejects the group's trial.  Accept and stop are mvp_trajectory_fit's rules on f_g:
+ *     mu_g = 1e-3 at the start, accepted when f_g(trial) is finite and <= f_g (mu_g <-
+ *     max(0.1·mu_g, 1e-12)), else mu_g <- 10·mu_g; converged (0x40 clear) at the first accepted
+ *     trial with f - f(trial) <= tol·f; stalled (0x40) when mu_g > 1e12; out of trials (0x40) after
+ *     max_iter (0..63) trials.  Group status bits 0-5 hold the number of trials.  A group is
+ *     accepted or rejected as a whole.  With max_iter = 0 the call returns the seed with f_g
+ *     evaluated there (0x40).
+ * Everything is fp64 on the device, FMA contraction allowed, no floating-point atomics: a segment's
+ * cost is counted once, at its end a; a chain's terms are summed per tile of 256 frames as
+ * mvp_trajectory_fit sums them, a group's chains in ascending order, the bones after the chains; the
+ * same inputs give the same bits on every call.  With J = 1 the call states mvp_trajectory_fit's
+ * problem: a chain whose cost at the seed is not finite is then an invalid group.  (With n_seg = 0
+ * and J > 1 the chains share no term, but a person's chains are still accepted, rejected and
+ * stopped together.)
+ * Convergence across the coupling is linear, at a rate set by β against the data curvature (about
+ * 5 per cm² per view with confidence weights on the synthetic two-camera rig): in the numpy
+ * prototype β = 1..10 converged in 18-32 trials at tol 1e-4, β = 100 did not in 60.  On that rig
+ * (120 frames, camera 1 losing the left elbow and wrist for 40 frames, λ = 0.25, β = 1, the 12
+ * segments of examples/body_part_lengths.yaml at their true lengths) the restatement in
+ * tests/skel_fit_ref.py and the device both end 3.3 cm RMS from the truth over the lost joints in
+ * 18 trials, where mvp_trajectory_smooth's blind fill is 17.0 cm and the fit without bones 65.8 cm
+ * off: a factor 5.2.  At T = 100 000, G = 1, J = 17, 12 segments, 2 views on one MI355X a trial
+ * takes 2.3-2.6 ms against mvp_trajectory_fit's 2.2-2.3 ms: the solve both share dominates, the
+ * bones add 0.1-0.2 ms in the linearise and cost kernels.
+ *
+ * mvp_skeleton_fit_plan : what a call with (T, P, J, chunk) will use: the chunk length, the chunks
+ *   per chain and the bytes of the caller-owned workspace (contents are scratch); any may be NULL.
+ * mvp_skeleton_fit_system : ONE linearisation at the given float32 trajectory xyz_dev [T][P][3]; no
+ *   solve, no state, no validity test (every segment with a live length is live).
+ *   out_H_dev [T][P][6] and out_g_dev [T][P][3] float64: H~_t and g~_t, data plus bone terms, β
+ *   applied; out_nviews_dev [T][P] uint8; out_cost_dev [G][3] float64: {Σ rho (+inf behind a
+ *   camera), the smoothness term with λ = 1, ½ Σ (r - L)², i.e. the bone term with β = 1}.  All
+ *   four are required.
+ * mvp_skeleton_fit : the whole optimisation from the seed xyz0_dev, stream-ordered, with no host
+ *   synchronisation, no allocation and no decision on the host: the number of launches is fixed
+ *   by max_iter.
+ *   out_xyz_dev [T][P][3] float32; out_resid_dev [T][P] float32 or NULL and out_nviews_dev [T][P]
+ *   uint8 or NULL as mvp_trajectory_fit's; out_bone_dev [T][G][n_seg] float32 or NULL: r - L at the
+ *   final state, NaN for a dead segment or an invalid group; out_cost_dev [G][4] float64 or NULL:
+ *   {f at the seed, f final, the bone term (β applied) at the seed, final};
+ *   out_group_status_dev [G] uint8 or NULL; out_chain_status_dev [P] uint8 (0 or 0x80) or NULL.
+ * Requires everything mvp_trajectory_fit requires, P a multiple of J, the seg_host rules above,
+ * β finite and >= 0, seg_len_dev not NULL when n_seg > 0.  Argument errors return MVP_ERR_ARG before
+ * any device work.
+ * Out of scope: the exact coupled Gauss-Newton step (for example conjugate gradients preconditioned
+ * by the per-chain solve); estimating the lengths inside the fit; joint-angle limits; the left /
+ * right depth flip that a single bone leaves open (the seed decides the side).
+ * ------------------------------------------------------------------------- */
+int mvp_skeleton_fit_plan(int T, int P, int J, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_skeleton_fit_system(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                            const int* cam_idx_host, int n_cam_idx, const float* xyz_dev, const uint8_t* mask_dev,
+                            int weights, const double* gauss_dev, float min_conf, float cov_floor, double huber_delta,
+                            int J, const int* seg_host, int n_seg, const float* seg_len_dev, double lambda_bone,
+                            double* out_H_dev, double* out_g_dev, uint8_t* out_nviews_dev, double* out_cost_dev,
+                            void* stream);
+int mvp_skeleton_fit(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                     const int* cam_idx_host, int n_cam_idx, const float* xyz0_dev, const uint8_t* mask_dev,
+                     int weights, const double* gauss_dev, float min_conf, float cov_floor, double huber_delta,
+                     double lambda_smooth, int J, const int* seg_host, int n_seg, const float* seg_len_dev,
+                     double lambda_bone, int max_iter, double tol, int chunk, void* workspace_dev,
+                     int64_t workspace_bytes, float* out_xyz_dev, float* out_resid_dev, uint8_t* out_nviews_dev,
+                     float* out_bone_dev, double* out_cost_dev, uint8_t* out_group_status_dev,
+                     uint8_t* out_chain_status_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
  * MPEG-4 Part 2 ('mp4v') decoding, host side — replaces cv.VideoCapture on the reference's

@@ -134,6 +134,14 @@ SIGNATURES = {
                                    c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_double, c_int, c_double,
                                    c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "mvp_skeleton_fit_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
+    "mvp_skeleton_fit_system": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p,
+                                        c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_int, P(c_int), c_int,
+                                        c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_skeleton_fit": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p, c_void_p,
+                                 c_int, c_void_p, c_float, c_float, c_double, c_double, c_int, P(c_int), c_int,
+                                 c_void_p, c_double, c_int, c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

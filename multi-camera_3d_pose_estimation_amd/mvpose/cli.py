@@ -205,8 +205,30 @@ def _load_if_exists(path):
     return np.load(path) if path is not None and os.path.exists(str(path)) else None
 
 
+def _camera_params(args):
+    """{index: [K, R, T, dist]} of the cameras named in the extrinsic parameter folder."""
+    cameras, _origin = geometry.load_camera_names(str(args.extrinsic_params_dir))
+    cam_params = {}
+    for i in cameras:
+        _, cam_params[i] = geometry.get_params_from_name(cameras[i], intrinsic_params_dir=str(
+            args.intrinsic_params_dir), extrinsic_params_dir=str(args.extrinsic_params_dir))
+    return cam_params
+
+
+def _body_lengths(args):
+    """The individual's {segment name: length} from the body-lengths YAML, or None."""
+    if args.ignore_body_lengths:
+        return None
+    if args.body_part_lengths_yaml is None and os.path.exists("./body_part_lengths.yaml"):
+        args.body_part_lengths_yaml = "./body_part_lengths.yaml"
+    if args.body_part_lengths_yaml is None:
+        return None
+    with open(args.body_part_lengths_yaml) as f:
+        return yaml.safe_load(f)[args.body_part_lengths_individual_name_yaml]
+
+
 def pose_refinement_main(argv=None):
-    from .refine import Optimized_3d_Pose_Estimation, linear_interpolation, smooth_trajectory
+    from .refine import SEGMENTS, Optimized_3d_Pose_Estimation, fit_skeleton, linear_interpolation, smooth_trajectory
     args = pose_refinement_parser(extensions=True).parse_args(argv)
     if args.run_path is None:
         args.run_path = os.getcwd()
@@ -237,18 +259,8 @@ def pose_refinement_main(argv=None):
         outputs["linear_interpolation"] = path
         types.discard("linear_interpolation")
     if "SGD" in types:
-        cameras, _origin = geometry.load_camera_names(str(args.extrinsic_params_dir))
-        cam_params = {}
-        for i in cameras:
-            _, cam_params[i] = geometry.get_params_from_name(cameras[i], intrinsic_params_dir=str(
-                args.intrinsic_params_dir), extrinsic_params_dir=str(args.extrinsic_params_dir))
-        my_lengths = None
-        if not args.ignore_body_lengths:
-            if args.body_part_lengths_yaml is None and os.path.exists("./body_part_lengths.yaml"):
-                args.body_part_lengths_yaml = "./body_part_lengths.yaml"
-            if args.body_part_lengths_yaml is not None:
-                with open(args.body_part_lengths_yaml) as f:
-                    my_lengths = yaml.safe_load(f)[args.body_part_lengths_individual_name_yaml]
+        cam_params = _camera_params(args)
+        my_lengths = _body_lengths(args)
         init = interp if args.interpolate_before_SGD else kpts_3d
         opt = Optimized_3d_Pose_Estimation(torch.tensor(heatmaps), init, decomposed_cam_params_initial=cam_params,
                                            body_lengths=my_lengths)
@@ -272,7 +284,30 @@ def pose_refinement_main(argv=None):
         np.save(os.path.join(args.save_path, "kpts_3d_smooth_resid.npy"), info["resid"])
         outputs["smooth"] = path
         types.discard("smooth")
+    if "skeleton_fit" in types:   # the 2D keypoints, the smoothness prior and the bone lengths, from the smoother's seed
+        from . import people
+        kw = prepare_kwargs(smooth_trajectory, params.get("smooth"))
+        kw.update({"cov": _load_if_exists(args.kpts_3d_cov), "status": _load_if_exists(args.kpts_3d_refine_status)})
+        seed = smooth_trajectory(kpts_3d, **kw)
+        my_lengths = _body_lengths(args)
+        if my_lengths is not None:
+            seg = {"body_lengths": my_lengths}
+        elif args.ignore_body_lengths:   # nobody measured them: the medians of the triangulated frames
+            pairs = np.array(list(SEGMENTS.values()), np.int32)
+            seg = {"segments": (pairs, people.estimate_bone_lengths(torch.as_tensor(kpts_3d), pairs))}
+        else:
+            raise ValueError("skeleton_fit needs --body_part_lengths_yaml, or --ignore_body_lengths to estimate the "
+                             "lengths from kpts_3d")
+        kw = prepare_kwargs(fit_skeleton, params.get("skeleton_fit"))
+        kw.update(seg, return_info=True)
+        fit, info = fit_skeleton(_load_if_exists(args.kpts_2d), _camera_params(args), seed, **kw)
+        path = os.path.join(args.save_path, "kpts_3d_skeleton_fit.npy")
+        print(f"saving skeleton fit at {path}")
+        np.save(path, fit)
+        np.save(os.path.join(args.save_path, "kpts_3d_skeleton_fit_resid.npy"), info["resid"])
+        outputs["skeleton_fit"] = path
+        types.discard("skeleton_fit")
     if types:
         raise ValueError(f"unknown refinement type(s) {sorted(types)}; expected linear_interpolation, SGD "
-                         "and/or smooth")
+                         "and/or smooth, skeleton_fit")
     return outputs

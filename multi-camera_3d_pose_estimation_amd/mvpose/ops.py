@@ -633,3 +633,94 @@ def trajectory_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int
          float(lambda_smooth), int(max_iter), float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out),
          _ptr(resid), _ptr(nviews), _ptr(cost), _ptr(status), _stream(dev))
     return out, resid, nviews, cost, status
+
+
+def skeleton_fit_plan(T: int, P: int, J: int, chunk: int = 0):
+    """What skeleton_fit will use for (T, P, J, chunk) (mvp_skeleton_fit_plan): the chunk length of
+    its time-parallel solve, the chunks per chain and the workspace bytes."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_skeleton_fit_plan", int(T), int(P), int(J), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
+         ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
+def _skeleton_args(P, J, pairs, lengths, dev):
+    """The segment arguments of the two skeleton-fit calls: the host pair table and the (G, n_seg)
+    float32 lengths on the device."""
+    J = int(J)
+    if J < 1 or P % J:
+        raise ValueError(f"P={P} must be a multiple of J={J} >= 1")
+    G = P // J
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n_seg = pr.shape[0]
+    seg = (ctypes.c_int * max(2 * n_seg, 1))(*pr.reshape(-1).tolist())
+    ln = torch.as_tensor(lengths, dtype=torch.float32, device=dev)
+    if ln.dim() == 1:
+        ln = ln.unsqueeze(0).expand(G, -1)
+    if tuple(ln.shape) != (G, n_seg):
+        raise ValueError(f"lengths must be {(n_seg,)} or {(G, n_seg)}, got {tuple(ln.shape)}")
+    return J, G, seg, n_seg, ln.contiguous()
+
+
+def skeleton_fit_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz: torch.Tensor,
+                        J: int, pairs, lengths, *, lambda_bone: float = 1.0, weights: str = "conf",
+                        gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None, min_conf: float = 0.0,
+                        cov_floor: float = 1.0, huber_delta: float = 0.0):
+    """One linearisation of the skeleton fit (mvp_skeleton_fit_system; stated in include/mvpose.h) at
+    the float32 trajectory xyz (T, P, 3), P = G·J, chain g·J + j the joint j of person g.
+
+    pairs (n_seg, 2) int: the joints a segment joins; lengths (n_seg,) or (G, n_seg) float32: a
+    length that is not finite or not > 0 switches the segment off for that person.  The other
+    arguments as for trajectory_fit_system.  Returns (H (T, P, 6) float64 and g (T, P, 3) float64:
+    the data term plus the bone terms with lambda_bone applied; nviews (T, P) uint8; cost (G, 3)
+    float64: Σ rho, ½ Σ |second difference|², ½ Σ (r − L)²), all on the GPU."""
+    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    dev = kpts.device
+    J, G, seg, n_seg, ln = _skeleton_args(P, J, pairs, lengths, dev)
+    H = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
+    g = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    cost = torch.empty((G, 3), dtype=torch.float64, device=dev)
+    call("mvp_skeleton_fit_system", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
+         J, seg, n_seg, _ptr(ln) if n_seg else None, float(lambda_bone), _ptr(H), _ptr(g), _ptr(nviews), _ptr(cost),
+         _stream(dev))
+    return H, g, nviews, cost
+
+
+def skeleton_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz0: torch.Tensor, J: int, pairs,
+                 lengths, *, lambda_bone: float = 1.0, weights: str = "conf", gauss: torch.Tensor | None = None,
+                 mask: torch.Tensor | None = None, min_conf: float = 0.0, cov_floor: float = 1.0,
+                 huber_delta: float = 0.0, lambda_smooth: float = 1.0, max_iter: int = 30, tol: float = 1e-6,
+                 chunk: int = 0):
+    """The trajectory fit with each person's joints coupled by bone lengths (mvp_skeleton_fit; stated
+    in include/mvpose.h): per person the minimiser of the chains' trajectory-fit costs plus
+    ½ lambda_bone Σ_t Σ_segments (|X_b − X_a| − L)², by Levenberg-Marquardt from the seed xyz0
+    (T, P, 3) float32, one damping factor and one accept / reject per person.  Arguments as for
+    skeleton_fit_system and trajectory_fit.  Stream-ordered, no host synchronisation.
+
+    Returns (xyz (T, P, 3) float32; resid (T, P) float32; nviews (T, P) uint8; bone (T, G, n_seg)
+    float32: r − L at the result, NaN for a segment that is off; cost (G, 4) float64: the cost at the
+    seed and at the result, the bone part of each; group_status (G,) uint8: bits 0-5 the trials, 0x40
+    not converged, 0x80 invalid; chain_status (P,) uint8: 0x80 for a chain returned as its seed), all
+    on the GPU."""
+    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask)
+    dev = kpts.device
+    J, G, seg, n_seg, ln = _skeleton_args(P, J, pairs, lengths, dev)
+    _, _, nbytes = skeleton_fit_plan(T, P, J, chunk)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((T, P, 3), dtype=torch.float32, device=dev)
+    resid = torch.empty((T, P), dtype=torch.float32, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    bone = torch.empty((T, G, n_seg), dtype=torch.float32, device=dev)
+    cost = torch.empty((G, 4), dtype=torch.float64, device=dev)
+    gstatus = torch.empty((G,), dtype=torch.uint8, device=dev)
+    cstatus = torch.empty((P,), dtype=torch.uint8, device=dev)
+    call("mvp_skeleton_fit", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
+         float(lambda_smooth), J, seg, n_seg, _ptr(ln) if n_seg else None, float(lambda_bone), int(max_iter),
+         float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out), _ptr(resid), _ptr(nviews), _ptr(bone), _ptr(cost),
+         _ptr(gstatus), _ptr(cstatus), _stream(dev))
+    return out, resid, nviews, bone, cost, gstatus, cstatus

@@ -159,3 +159,29 @@ def person_trajectories(track: torch.Tensor, arrays: dict, min_len: int = 1, max
         keep = present.reshape(present.shape + (1,) * (a.dim() - 2))
         out[name] = torch.where(keep, got, torch.full((), fill, dtype=a.dtype, device=dev))
     return out, present, chosen
+
+
+def estimate_bone_lengths(xyz: torch.Tensor, pairs, valid: torch.Tensor | None = None, min_frames: int = 10):
+    """Segment lengths of each person from their own 3D points, for skeleton_fit when nobody measured
+    them: per person and segment the median over the frames of |X_b − X_a| where both ends are
+    finite (and valid), e.g. the two-view frames of kpts_3d.  xyz (T, J, 3) or (T, Np, J, 3); pairs
+    (n_seg, 2); valid (T, [Np,] J) bool or None.  Returns float32 (n_seg,) or (Np, n_seg) on xyz's
+    device; NaN where fewer than min_frames frames have the segment, which switches it off in
+    skeleton_fit.  Torch only, no host synchronisation."""
+    if xyz.dim() not in (3, 4) or xyz.shape[-1] != 3:
+        raise ValueError(f"xyz must be (T, J, 3) or (T, Np, J, 3), got {tuple(xyz.shape)}")
+    pr = torch.as_tensor(np.asarray(pairs, dtype=np.int64).reshape(-1, 2), device=xyz.device)
+    x = xyz.to(torch.float32)
+    ok = torch.isfinite(x).all(-1)
+    if valid is not None:
+        if tuple(valid.shape) != tuple(xyz.shape[:-1]):
+            raise ValueError(f"valid must be {tuple(xyz.shape[:-1])}, got {tuple(valid.shape)}")
+        ok = ok & valid.to(device=xyz.device, dtype=torch.bool)
+    a, b = pr[:, 0], pr[:, 1]
+    d = torch.linalg.vector_norm(x.index_select(-2, b) - x.index_select(-2, a), dim=-1)       # (T, [Np,] n_seg)
+    both = ok.index_select(-1, a) & ok.index_select(-1, b)
+    d = torch.where(both, d, torch.full((), float("nan"), dtype=d.dtype, device=d.device))
+    if d.shape[-1] == 0 or d.shape[0] == 0:
+        return torch.full(d.shape[1:], float("nan"), dtype=torch.float32, device=d.device)
+    med = torch.nanmedian(d, dim=0).values
+    return torch.where(both.sum(0) >= int(min_frames), med, torch.full_like(med, float("nan")))

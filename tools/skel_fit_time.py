@@ -1,0 +1,167 @@
+#!/usr/bin/env python
+"""Times mvp_skeleton_fit on the GPU beside mvp_trajectory_fit from another build of the library.
+
+    python tools/skel_fit_time.py --parent-lib PATH/libmvpose.so [--T 100000] [--reps 3]
+                                  [--out profiles/skel_fit_time.txt]
+
+One person of 17 joints with the reference's 12 segments, (T, G, J) = (100 000, 1, 17), nv = 2 and 8
+listed views, confidence weights, lambda 1, beta 1.  A call is timed with max_iter = 0, 1, 2, 3 and a
+tolerance no run reaches, so that the group runs every trial; the differences are the first trial
+(solve, trial cost, sum, decide) and a later trial (the same plus the linearisation of the moved
+state).  mvp_trajectory_fit is timed the same way on the same inputs from --parent-lib, a build of
+the commit before the skeleton fit (it lacks the symbols mvpose._lib asks for, so both libraries
+are driven through plain ctypes, each in child processes of its own), alternating with this
+build's mvp_skeleton_fit, twice each.
+
+Device events around `reps` back-to-back calls after a warm-up, median [min, max] of 5 windows.
+Needs a GPU: no fallback."""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "multi-camera_3d_pose_estimation_amd")
+J = 17
+
+
+def time_call(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        out.append(a.elapsed_time(b) * 1e3 / reps)
+    return float(np.median(out)), float(min(out)), float(max(out))
+
+
+def fmt(t):
+    return f"{t[0]:.0f} [{t[1]:.0f} {t[2]:.0f}]"
+
+
+def child(kind, lib_path, inputs, reps):
+    """One library's mvp_skeleton_fit (kind "skel") or mvp_trajectory_fit ("fit") on the saved inputs
+    through plain ctypes: prints one JSON line {max_iter: (median, min, max)}, the status values and
+    a digest of the last output."""
+    lib = ctypes.CDLL(lib_path)
+    z = np.load(inputs)
+    dev = "cuda"
+    k, cams, x0 = (torch.tensor(z[n], device=dev) for n in ("kpts", "cams", "seed"))
+    lengths = torch.tensor(z["lengths"], device=dev)
+    pairs = z["pairs"].astype(np.int32)
+    T, P, _, V = k.shape
+    nv = int(z["nv"])
+    ci = (ctypes.c_int * nv)(*range(nv))
+    seg = (ctypes.c_int * pairs.size)(*pairs.reshape(-1).tolist())
+    vp = lambda a: ctypes.c_void_p(a.data_ptr())  # noqa: E731
+    I, D, F, VP, I64 = ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64
+    front = [VP, I, I, I, VP, I, ctypes.POINTER(I), I, VP, VP, I, VP, F, F, D, D]
+    nbytes = I64(0)
+    out = torch.empty((T, P, 3), dtype=torch.float32, device=dev)
+    stream = VP(torch.cuda.current_stream().cuda_stream)
+    if kind == "skel":
+        assert lib.mvp_skeleton_fit_plan(T, P, J, 0, None, None, ctypes.byref(nbytes)) == 0
+        lib.mvp_skeleton_fit.argtypes = front + [I, ctypes.POINTER(I), I, VP, D, I, D, I, VP, I64] + [VP] * 8
+        status = torch.empty((P // J,), dtype=torch.uint8, device=dev)
+    else:
+        assert lib.mvp_trajectory_fit_plan(T, P, 0, None, None, ctypes.byref(nbytes)) == 0
+        lib.mvp_trajectory_fit.argtypes = front + [I, D, I, VP, I64] + [VP] * 6
+        status = torch.empty((P,), dtype=torch.uint8, device=dev)
+    work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    head = (vp(k), T, P, V, vp(cams), cams.shape[0], ci, nv, vp(x0), None, 1, None, 0.0, 1.0, 0.0, 1.0)
+
+    def run(it):
+        if kind == "skel":
+            rc = lib.mvp_skeleton_fit(*head, J, seg, len(pairs), vp(lengths), 1.0, it, 1e-30, 0, vp(work), nbytes.value,
+                                      vp(out), None, None, None, None, vp(status), None, stream)
+        else:
+            rc = lib.mvp_trajectory_fit(*head, it, 1e-30, 0, vp(work), nbytes.value, vp(out), None, None, None, vp(status),
+                                        stream)
+        assert rc == 0
+    res = {}
+    for it in (0, 1, 2, 3):
+        res[it] = time_call(lambda: run(it), reps)
+    st = sorted(set(hex(s) for s in status.cpu().numpy()))
+    print(json.dumps({"us": res, "status": st, "sum": float(out.double().sum()), "workspace": nbytes.value,
+                      "device": torch.cuda.get_device_name(0)}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=100000)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "skel_fit_time.txt"))
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        if not torch.cuda.is_available():
+            sys.exit("skel_fit_time.py needs a GPU")
+        child(*args.child, args.reps)
+        return
+    if not args.parent_lib:
+        sys.exit("skel_fit_time.py needs --parent-lib, a libmvpose.so built from the commit before the skeleton fit")
+    for p in (ROOT, PKG):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    from mvpose import ops, synthetic as syn
+    from mvpose.refine import SEGMENTS
+    names = ["left_shoulder_left_elbow", "left_elbow_left_wrist", "right_shoulder_right_elbow", "right_elbow_right_wrist",
+             "left_hip_left_knee", "left_knee_left_ankle", "right_hip_right_knee", "right_knee_right_ankle",
+             "left_hip_right_hip", "left_shoulder_left_hip", "right_shoulder_right_hip", "left_shoulder_right_shoulder"]
+    pairs = np.array([SEGMENTS[n] for n in names], np.int32)
+    T = args.T
+    lines = []   # the parent process never touches the GPU: the children name the device
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    truth = syn.make_poses(T, seed=1, jitter=0.0)
+    rng = np.random.default_rng(2)
+    seed = (truth + rng.normal(0.0, 1.0, truth.shape)).astype(np.float32)
+    lengths = np.array([[np.linalg.norm(truth[0, b] - truth[0, a]) for a, b in pairs]], np.float32)
+    here = os.path.join(PKG, "mvpose", "libmvpose.so")
+    with tempfile.TemporaryDirectory() as tmp:
+        for nv in (2, 8):
+            cams = syn.make_rig(nv, seed=3)
+            kpts = syn.make_kpts_2d(truth, cams, seed=3, noise_px=1.0)
+            gone = rng.uniform(size=(T, J, nv)) < 0.2
+            gone[..., 0] &= rng.uniform(size=(T, J)) < 0.5      # view 0 less often: most frames keep >= 1 view
+            kpts[:, :, 0, :][gone] = np.nan
+            inputs = os.path.join(tmp, f"nv{nv}.npz")
+            np.savez(inputs, kpts=kpts, cams=ops.pack_cameras(syn.reference_camera_params(cams)), seed=seed,
+                     lengths=lengths, pairs=pairs, nv=nv)
+            for kind, lib in (("fit", args.parent_lib), ("skel", here)) * 2:
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", kind, lib, inputs, "--reps",
+                                    str(args.reps)], capture_output=True, text=True, timeout=600)
+                if r.returncode != 0:
+                    sys.exit(f"child {kind} for {lib} failed:\n{r.stderr[-2000:]}")
+                j = json.loads(r.stdout.strip().splitlines()[-1])
+                t = {int(k): v for k, v in j["us"].items()}
+                if not lines:
+                    emit(f"# mvp_skeleton_fit beside the parent build's mvp_trajectory_fit, {j['device']}, device events, "
+                         f"median [min max] of 5 windows of {args.reps} calls, us")
+                what = "mvp_trajectory_fit, parent build" if kind == "fit" else "mvp_skeleton_fit, this build  "
+                emit(f"T={T} G=1 J={J} n_seg={len(pairs)} nv={nv} {what}: max_iter=0 {fmt(t[0])}; 1 {fmt(t[1])}; 2 {fmt(t[2])}; "
+                     f"3 {fmt(t[3])}; seed path {t[0][0]:.0f}; first trial {t[1][0] - t[0][0]:.0f}; a later trial "
+                     f"{t[2][0] - t[1][0]:.0f} and {t[3][0] - t[2][0]:.0f}; status after 3 {j['status']}; workspace "
+                     f"{j['workspace'] / 1e6:.0f} MB; sum of the output {j['sum']!r}")
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
