@@ -612,6 +612,41 @@ int mvp_trajectory_smooth(const float* xyz_dev, const float* cov_dev, const uint
                           uint8_t* out_observed_dev, uint8_t* out_status_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Posterior covariance of the smoothed trajectory (no reference counterpart).
+ *
+ * With A = blockdiag(W) + λ·(D₂ᵀD₂ ⊗ I₃), exactly mvp_trajectory_smooth's matrix (the same observed
+ * rule, W_t, sigma0 and cov_floor), the smoothed X is the mean of a Gaussian with covariance
+ * Σ = A⁻¹: the exact posterior of that model.  The call returns its 3x3 diagonal blocks Σ_{t,t} and
+ * its lag-1 blocks Σ_{t,t+1}, in world units², for EVERY frame: an unobserved frame has a
+ * covariance too, held by the prior and its observed neighbours, and it grows towards the middle of
+ * a gap.  Σ does not depend on the coordinates beyond whether they are finite.
+ *
+ * The factorisation is mvp_trajectory_smooth's (partition method, same elimination order); the
+ * blocks of Σ come from the Takahashi recursion run back over its factors, every symmetric block
+ * held as a packed triangle (csrc/smooth_solver.h).  fp64, FMA contraction
+ * allowed; the result does not depend on chunk beyond fp64 rounding.
+ *
+ * Failure: mvp_trajectory_smooth's rules (fewer than 2 observed frames, or a pivot not > 0).  A
+ * failed chain gets NaN in all of out_cov and out_cross and status 0x80; other chains status 0.
+ *
+ * mvp_trajectory_smooth_cov_plan : as mvp_trajectory_smooth_plan, for this call's (larger)
+ *   workspace.
+ * mvp_trajectory_smooth_cov : inputs as mvp_trajectory_smooth.  out_cov_dev [T][P][6] f32, required:
+ *   (xx, xy, xz, yy, yz, zz) of Σ_{t,t}; out_cross_dev [T][P][9] f32 or NULL: Σ_{t,t+1} row-major,
+ *   row = coordinate of X_t, column = coordinate of X_{t+1}, NaN at t = T−1; out_status_dev [P]
+ *   uint8 or NULL.  Requires what mvp_trajectory_smooth requires; argument errors return
+ *   MVP_ERR_ARG before any device work.  Stream-ordered: no host synchronisation and no allocation.
+ * Time, one MI355X, T = 100 000, P = 17, chunk 0: 3.65 ms against mvp_trajectory_smooth's 2.46 ms on
+ * the same inputs, 1.49x.
+ * Out of scope: blocks further than lag 1; uncertainty of λ itself.
+ * ------------------------------------------------------------------------- */
+int mvp_trajectory_smooth_cov_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_trajectory_smooth_cov(const float* xyz_dev, const float* cov_dev, const uint8_t* valid_dev, int T, int P,
+                              double lambda_smooth, float sigma0, float cov_floor, int chunk, void* workspace_dev,
+                              int64_t workspace_bytes, float* out_cov_dev, float* out_cross_dev,
+                              uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Epipolar lag-cost scan: the data term of pose-based frame synchronisation (no reference
  * counterpart; the reference synchronises by hand, synchronize_videos.py).  For a calibrated pair
  * of cameras, keypoints of the same joint satisfy the epipolar constraint only when their frames
@@ -927,8 +962,21 @@ int mvp_bundle_adjust(const float* kpts_dev, int64_t n_points, int V, const doub
  * Requires T >= 1, P >= 1, T·P < 2^31, 2 <= n_cam_idx <= 8, lambda_smooth and tol finite and > 0,
  * cov_floor >= 0, min_conf and huber_delta not NaN (huber_delta <= 0: off), 0 <= max_iter <= 63,
  * chunk = 0 or 4..4096.  Argument errors return MVP_ERR_ARG before any device work.
- * Out of scope: a posterior covariance of the trajectory (it needs the selected inverse of A, not
- * a solve); sub-frame time offsets between the cameras (mvp_epipolar_lag_cost finds whole frames);
+ * mvp_trajectory_fit_cov_plan, mvp_trajectory_fit_cov : the covariance of a fitted trajectory.  With
+ *   A = blockdiag(H~) + λ·(D₂ᵀD₂ ⊗ I₃), H~ this fit's linearisation at the given xyz_dev (normally
+ *   the fit's output; the used-view rules and the IRLS weights ω of huber_delta as above, no
+ *   Marquardt factor), the call returns the diagonal and lag-1 blocks of Σ = A⁻¹.  This is the
+ *   Gauss-Newton / Laplace covariance at that state: exact for the linearised model with the
+ *   weights frozen there, not the posterior of the robust nonlinear cost.  A chain fails, with NaN
+ *   in all of out_cov and out_cross and status 0x80 (others 0), when xyz_dev is not finite in some
+ *   frame, a used view has P_z <= 0 there, fewer than 2 frames have >= 2 used views, or a pivot is
+ *   not > 0.  Outputs, units and layout as mvp_trajectory_smooth_cov; out_cov_dev is required.
+ *   Requires what mvp_trajectory_fit requires of the arguments both have.  Stream-ordered, no
+ *   allocation, no host synchronisation.  Time, one MI355X, T = 100 000, P = 17, two views, chunk 0:
+ *   3.71 ms against 2.23 ms for one trial of mvp_trajectory_fit, 1.67x.
+ * Out of scope: blocks of Σ further than lag 1, the uncertainty of λ itself, and a covariance for
+ * mvp_skeleton_fit (its chains are coupled: the per-chain inverse is not its posterior); sub-frame
+ * time offsets between the cameras (mvp_epipolar_lag_cost finds whole frames);
  * coupling between chains such as bone lengths (chains stay independent here; mvp_skeleton_fit
  * below couples them).
  * ------------------------------------------------------------------------- */
@@ -944,6 +992,12 @@ int mvp_trajectory_fit(const float* kpts_dev, int T, int P, int V, const double*
                        double lambda_smooth, int max_iter, double tol, int chunk, void* workspace_dev,
                        int64_t workspace_bytes, float* out_xyz_dev, float* out_resid_dev, uint8_t* out_nviews_dev,
                        double* out_cost_dev, uint8_t* out_status_dev, void* stream);
+int mvp_trajectory_fit_cov_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_trajectory_fit_cov(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                           const int* cam_idx_host, int n_cam_idx, const float* xyz_dev, const uint8_t* mask_dev,
+                           int weights, const double* gauss_dev, float min_conf, float cov_floor, double huber_delta,
+                           double lambda_smooth, int chunk, void* workspace_dev, int64_t workspace_bytes,
+                           float* out_cov_dev, float* out_cross_dev, uint8_t* out_status_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The trajectory fit with a person's joints coupled by bone lengths: the third of the costs the

@@ -38,6 +38,11 @@
 // The three sweeps' per-lane code and the plan are in smooth_solver.h, templated on the frame
 // source (the trajectory fit runs them over an information-form buffer); here: the smoother's
 // source, (xyz, cov, valid) -> (W, z) and the outputs, its kernels and the C entry points.
+//
+// mvp_trajectory_smooth_cov runs the same eliminate and reduce over the same frames with the
+// inverse pivots kept, the reduced system's selected inverse behind the reduce, and the covariance
+// sweep (smooth_solver.h: reduce_cov_chain, cov_lane) where the smoother has its
+// backsub: the diagonal and lag-1 blocks of the inverse of the smoother's matrix.
 #include "smooth_solver.h"
 
 namespace {
@@ -171,6 +176,44 @@ struct SmoothArgs : SmoothSrc {
     }
 };
 
+// The source of mvp_trajectory_smooth_cov: the same frames and weights, the inverse pivots kept,
+// and the covariance outputs where the smoother has its own (which stay null: no backsub runs).
+struct SmoothCovArgs : SmoothSrc, CovCore {
+    using Raw = RawFrame;
+    static constexpr bool kInfoForm = false;
+    static constexpr bool kKeepPivot = true;
+    MVP_SMOOTH_HD NoDamp damp(int) const { return NoDamp{}; }
+    MVP_SMOOTH_HD bool skip(int) const { return false; }
+    MVP_SMOOTH_HD RawFrame load_raw(int t, int p) const { return ::load_raw(*this, t, p); }
+    MVP_SMOOTH_HD bool frame_weight(const RawFrame& f, double (&W)[6], double (&z)[3]) const {
+        return ::frame_weight(*this, f, W, z);
+    }
+    MVP_SMOOTH_HD void finish(int p, int cnt, int bad) const {
+        const int failed = (cnt < 2 || bad) ? 1 : 0;
+        fail[p] = failed;
+        if (out_status) out_status[p] = failed ? 0x80 : 0;
+    }
+    MVP_SMOOTH_HD bool failed(int p) const { return fail[p] != 0; }
+};
+
+__global__ __launch_bounds__(kSmBlock) void smooth_cov_eliminate_kernel(SmoothCovArgs a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) eliminate_lane(a, lane);
+}
+
+__global__ __launch_bounds__(kSmBlock) void smooth_cov_reduce_kernel(SmoothCovArgs a) {
+    const int p = blockIdx.x * kSmBlock + threadIdx.x;
+    if (p < a.P) {
+        reduce_chain(a, p);
+        reduce_cov_chain(a, p);
+    }
+}
+
+__global__ __launch_bounds__(kSmBlock) void smooth_cov_kernel(SmoothCovArgs a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) cov_lane(a, lane);
+}
+
 __global__ __launch_bounds__(kSmBlock) void smooth_eliminate_kernel(SmoothArgs a) {
     const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
     if (lane < a.n_lanes) eliminate_lane(a, lane);
@@ -246,6 +289,72 @@ extern "C" int mvp_trajectory_smooth(const float* xyz, const float* cov, const u
     hipLaunchKernelGGL(smooth_reduce_kernel, dim3((unsigned)((P + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, s, a);
     MVP_HIP(hipGetLastError());
     hipLaunchKernelGGL(smooth_backsub_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
+    MVP_HIP(hipGetLastError());
+    MVP_ABI_END
+}
+
+// The posterior covariance of the same model: eliminate (pivots kept), reduce + the reduced
+// system's selected inverse, then the covariance sweep where the smoother has its backsub.
+extern "C" int mvp_trajectory_smooth_cov_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks,
+                                              int64_t* workspace_bytes) {
+    MVP_ABI_BEGIN
+    const SmoothPlan pl = smooth_plan("mvp_trajectory_smooth_cov_plan", T, P, chunk);
+    const CovPlan cp = cov_plan(pl, P, pl.bytes);
+    if (chunk_used) *chunk_used = pl.chunk;
+    if (n_chunks) *n_chunks = pl.n_chunks;
+    if (workspace_bytes) *workspace_bytes = cp.bytes;
+    MVP_ABI_END
+}
+
+extern "C" int mvp_trajectory_smooth_cov(const float* xyz, const float* cov, const uint8_t* valid, int T, int P,
+                                         double lambda_smooth, float sigma0, float cov_floor, int chunk, void* workspace,
+                                         int64_t workspace_bytes, float* out_cov, float* out_cross, uint8_t* out_status,
+                                         void* stream) {
+    MVP_ABI_BEGIN
+    const char* fn = "mvp_trajectory_smooth_cov";
+    const SmoothPlan pl = smooth_plan(fn, T, P, chunk);
+    const CovPlan cp = cov_plan(pl, P, pl.bytes);
+    MVP_REQUIRE(std::isfinite(lambda_smooth) && lambda_smooth > 0, "%s: lambda_smooth=%g must be finite and > 0", fn,
+                lambda_smooth);
+    MVP_REQUIRE(std::isfinite(sigma0) && sigma0 > 0, "%s: sigma0=%g must be finite and > 0", fn, (double)sigma0);
+    MVP_REQUIRE(cov_floor >= 0, "%s: cov_floor=%g must be >= 0", fn, (double)cov_floor);
+    MVP_REQUIRE(workspace_bytes >= cp.bytes, "%s: workspace_bytes=%lld < %lld needed (T=%d, P=%d, chunk=%d)", fn,
+                (long long)workspace_bytes, (long long)cp.bytes, T, P, pl.chunk);
+    MVP_REQUIRE(xyz && out_cov && workspace, "%s: null device pointer", fn);
+    char* ws = static_cast<char*>(workspace);
+    SmoothCovArgs a{};
+    a.xyz = xyz;
+    a.cov = cov;
+    a.valid = valid;
+    a.T = T;
+    a.P = P;
+    a.chunk = pl.chunk;
+    a.n_chunks = pl.n_chunks;
+    a.n_seps = pl.n_seps;
+    a.n_lanes = pl.n_lanes;
+    a.n_blocks = pl.n_blocks;
+    a.lambda = lambda_smooth;
+    a.w0 = 1.0 / ((double)sigma0 * (double)sigma0);
+    a.cov_floor = (double)cov_floor;
+    a.fac = reinterpret_cast<double*>(ws + pl.off_fac);
+    a.schur = reinterpret_cast<double*>(ws + pl.off_schur);
+    a.red = reinterpret_cast<double*>(ws + pl.off_red);
+    a.usol = reinterpret_cast<double*>(ws + pl.off_usol);
+    a.cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
+    a.bad = reinterpret_cast<int*>(ws + pl.off_bad);
+    a.fail = reinterpret_cast<int*>(ws + pl.off_fail);
+    a.out_status = out_status;
+    a.piv = reinterpret_cast<double*>(ws + cp.off_piv);
+    a.covred = reinterpret_cast<double*>(ws + cp.off_covred);
+    a.out_cov = out_cov;
+    a.out_cross = out_cross;
+    hipStream_t s = (hipStream_t)stream;
+    MVP_HIP(hipMemsetAsync(a.cnt, 0, (size_t)P * 8, s));
+    hipLaunchKernelGGL(smooth_cov_eliminate_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(smooth_cov_reduce_kernel, dim3((unsigned)((P + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, s, a);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(smooth_cov_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
     MVP_HIP(hipGetLastError());
     MVP_ABI_END
 }

@@ -13,6 +13,12 @@
 //     load_out(t, p), write_frame(t, p, out, x0, x1, x2), failed(p), write_failed(t, p)   backsub
 //     finish(p, cnt, bad)           the end of the reduce: per-chain status
 //
+// A source that sets kKeepPivot = true and has the fields of CovCore gets the posterior covariance
+// instead of the solution: eliminate_lane then also stores each frame's inverse pivot, and
+// reduce_cov_chain / cov_lane (below) run the Takahashi recursion back over the same factors to
+// the diagonal and lag-1 blocks of A⁻¹.  Such a source needs failed(p) and none of the backsub
+// members.
+//
 // The per-lane functions also compile for the host, where a CPU build can step through them.
 #pragma once
 // FMA contraction is allowed in everything below, whatever an earlier header left in force
@@ -22,6 +28,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #define MVP_SMOOTH_HD __host__ __device__ __forceinline__
 
@@ -31,6 +38,8 @@ constexpr int kSmBlock = 64;         // threads per block: few lanes exist (P·n
 constexpr int kFacDoubles = 39;      // per eliminated frame: G (12x3) | q (3)
 constexpr int kSchurDoubles = 90;    // per lane: lower triangle of the 12x12 Schur complement (78) | rhs (12)
 constexpr int kRedDoubles = 63;      // per separator and chain: C (21, lower, 1/diagonal) | Y (36) | y (6)
+constexpr int kPivDoubles = 6;       // per eliminated frame of a covariance call: the inverse pivot (xx, xy, xz, yy, yz, zz)
+constexpr int kCovRedDoubles = 57;   // per separator and chain: Σ_jj (21, lower) | Σ_j,j+1 (36, row: coordinate of j)
 constexpr int kMinChunk = 4, kMaxChunk = 4096;
 
 // What the three sweeps need whatever the frames come from.
@@ -46,7 +55,24 @@ struct SolveCore {
     int* bad;       // [P] a pivot was not > 0 (zeroed likewise)
 };
 
+// What a covariance source adds to SolveCore.
+struct CovCore {
+    double* piv;        // [step][block][6][64]
+    double* covred;     // [sep][57][P]
+    float* out_cov;     // [T][P][6]
+    float* out_cross;   // [T][P][9] or null
+};
+
+// A::kKeepPivot, false where the source has no such member.
+template <class A, class = void>
+struct keeps_pivot : std::false_type {};
+template <class A>
+struct keeps_pivot<A, std::enable_if_t<A::kKeepPivot>> : std::true_type {};
+
 MVP_SMOOTH_HD constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
+MVP_SMOOTH_HD constexpr int sym(int i, int j) { return i >= j ? tri(i, j) : tri(j, i); }
+// index of (d, e), d >= e, in a 3x3 kept as (xx, xy, xz, yy, yz, zz)
+MVP_SMOOTH_HD constexpr int sym3(int d, int e) { return e == 0 ? d : e == 1 ? 2 + d : 5; }
 
 // 1/sqrt(s), s > 0 and normal, to ~1 ulp: v_rsq_f64 + two Newton steps on the device (a sixth of
 // the instructions of an fp64 sqrt followed by an fp64 division; every sweep step has six of them
@@ -96,6 +122,10 @@ MVP_SMOOTH_HD bool spd3_inverse(const double (&s)[6], double (&w)[6]) {
 template <class A>
 MVP_SMOOTH_HD int64_t fac_index(const A& a, int step, int64_t lane) {
     return (((int64_t)step * a.n_blocks + lane / kSmBlock) * kFacDoubles) * kSmBlock + lane % kSmBlock;
+}
+template <class A>
+MVP_SMOOTH_HD int64_t piv_index(const A& a, int step, int64_t lane) {
+    return (((int64_t)step * a.n_blocks + lane / kSmBlock) * kPivDoubles) * kSmBlock + lane % kSmBlock;
 }
 MVP_SMOOTH_HD int64_t schur_index(int64_t lane) {
     return (lane / kSmBlock) * kSchurDoubles * kSmBlock + lane % kSmBlock;
@@ -227,6 +257,11 @@ MVP_SMOOTH_HD void eliminate_lane(const A& a, int64_t lane) {
         f[36 * kSmBlock] = q0;
         f[37 * kSmBlock] = q1;
         f[38 * kSmBlock] = q2;
+        if constexpr (keeps_pivot<A>::value) {
+            double* pv = a.piv + piv_index(a, i, lane);
+#pragma unroll
+            for (int k = 0; k < kPivDoubles; k++) pv[k * kSmBlock] = Pi[k];
+        }
         // Schur update of the 12 remaining rows, shifted into place: rows 9..14 move to 6..11
 #pragma unroll
         for (int o = 0; o < 12; o++) {
@@ -465,6 +500,260 @@ MVP_SMOOTH_HD void backsub_lane(const A& a, int64_t lane) {
     }
 }
 
+// ----------------------------------------------------------------- posterior covariance
+// Σ = A⁻¹ by the Takahashi recursion over the factors of eliminate_lane and reduce_chain, in their
+// elimination order backwards: the separators first (reduce_cov_chain), then every chunk's
+// interior (cov_lane).  Every symmetric block is a packed lower triangle from the moment it is
+// formed: a 3x3 Π + GᵀΣG kept as a full matrix carries an antisymmetric rounding residue that the
+// recursion doubles per frame.
+
+// The selected inverse of chain p's reduced system: with D_j = C_j C_jᵀ, Y_j = C_j⁻¹ E_j and
+// Z_j = C_j⁻ᵀ Y_j,  Σ_last,last = C⁻ᵀ C⁻¹,  Σ_j,j+1 = −Z_j Σ_j+1,j+1,
+// Σ_j,j = C_j⁻ᵀ C_j⁻¹ + Z_j Σ_j+1,j+1 Z_jᵀ.  Runs behind reduce_chain (same lane: it reads red and
+// the chain's status).
+template <class A>
+MVP_SMOOTH_HD void reduce_cov_chain(const A& a, int p) {
+    const int ns = a.n_seps;
+    if (ns == 0 || a.failed(p)) return;
+    constexpr int kIn = 57;   // C | Y of red
+    double S[21], cur[kIn], nxt[kIn];
+    {
+        const double* rd = a.red + ((int64_t)(ns - 1) * kRedDoubles) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < kIn; i++) cur[i] = rd[(int64_t)i * a.P];
+    }
+#pragma unroll
+    for (int i = 0; i < 21; i++) S[i] = 0.0;
+    for (int j = ns - 1; j >= 0; j--) {
+        if (j > 0) {
+            const double* rd = a.red + ((int64_t)(j - 1) * kRedDoubles) * a.P + p;
+#pragma unroll
+            for (int i = 0; i < kIn; i++) nxt[i] = rd[(int64_t)i * a.P];
+        }
+        // Ci = C⁻¹ (lower), W = Ciᵀ Ci
+        double Ci[21], W[21];
+#pragma unroll
+        for (int i = 0; i < 6; i++) {
+            Ci[tri(i, i)] = cur[tri(i, i)];
+#pragma unroll
+            for (int u = 0; u < i; u++) {
+                double d = 0.0;
+#pragma unroll
+                for (int m = u; m < i; m++) d += cur[tri(i, m)] * Ci[tri(m, u)];
+                Ci[tri(i, u)] = -d * cur[tri(i, i)];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int u = 0; u <= i; u++) {
+                double d = 0.0;
+#pragma unroll
+                for (int m = i; m < 6; m++) d += Ci[tri(m, i)] * Ci[tri(m, u)];
+                W[tri(i, u)] = d;
+            }
+        double* cr = a.covred + ((int64_t)j * kCovRedDoubles) * a.P + p;
+        if (j + 1 < ns) {
+            double Z[36], X[36];
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int u = 0; u < 6; u++) {
+                    double d = 0.0;
+#pragma unroll
+                    for (int m = i; m < 6; m++) d += Ci[tri(m, i)] * cur[21 + 6 * m + u];
+                    Z[6 * i + u] = d;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int u = 0; u < 6; u++) {
+                    double d = 0.0;
+#pragma unroll
+                    for (int m = 0; m < 6; m++) d += Z[6 * i + m] * S[sym(m, u)];
+                    X[6 * i + u] = d;
+                    cr[(int64_t)(21 + 6 * i + u) * a.P] = -d;
+                }
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int u = 0; u <= i; u++) {
+                    double d = W[tri(i, u)];
+#pragma unroll
+                    for (int m = 0; m < 6; m++) d += X[6 * i + m] * Z[6 * u + m];
+                    W[tri(i, u)] = d;
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < 21; i++) {
+            S[i] = W[i];
+            cr[(int64_t)i * a.P] = W[i];
+        }
+        if (j > 0) {
+#pragma unroll
+            for (int i = 0; i < kIn; i++) cur[i] = nxt[i];
+        }
+    }
+}
+
+// Σ_t,t of frame (t, p) from a packed block; rows o.. of S, or the 3x3 form of the pivot.
+template <class A>
+MVP_SMOOTH_HD void put_cov(const A& a, int t, int p, double xx, double xy, double xz, double yy, double yz, double zz) {
+    float* o = a.out_cov + 6 * ((int64_t)t * a.P + p);
+    o[0] = (float)xx, o[1] = (float)xy, o[2] = (float)xz, o[3] = (float)yy, o[4] = (float)yz, o[5] = (float)zz;
+}
+
+// Σ_t,t+1 of frame (t, p), row-major (row: coordinate of X_t); NaN for the last frame.
+template <class A>
+MVP_SMOOTH_HD void put_cross(const A& a, int t, int p, const double (&c)[9]) {
+    if (!a.out_cross) return;
+    float* o = a.out_cross + 9 * ((int64_t)t * a.P + p);
+    const bool last = t == a.T - 1;
+#pragma unroll
+    for (int k = 0; k < 9; k++) o[k] = last ? NAN : (float)c[k];
+}
+
+// One lane per (chain, chunk), as backsub_lane: where that carries the solution on (left
+// separator, b, c), this carries Σ on them, a packed 12x12.  Per frame a, from the last interior
+// frame back:  Σ_N,a = −Σ_N,N G,  Σ_a,a = Π + Gᵀ Σ_N,N G,  then the window shifts to (L, a, b).
+// The lane writes Σ_t,t of the frames it owns and Σ_t,t+1 of every pair it holds in one window:
+// its interior frames, the first frame of its right separator, and the frame in front of its first
+// interior frame; the second separator frame's only when it ends the recording (NaN).
+template <class A>
+MVP_SMOOTH_HD void cov_lane(const A& a, int64_t lane) {
+    const LaneRange R = lane_range(a, lane);
+    const int p = R.p;
+    if (a.failed(p)) {
+        const double nan9[9] = {NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN};
+        for (int t = R.g0; t < R.hi; t++) put_cov(a, t, p, NAN, NAN, NAN, NAN, NAN, NAN);
+        for (int t = R.k > 0 ? R.g0 - 1 : R.g0; t < R.hi; t++)
+            if (t != R.g0 + R.n + 1 || t == a.T - 1) put_cross(a, t, p, nan9);
+        return;
+    }
+    // S: 0..5 left separator, 6..11 frames b, c (the right separator to start with)
+    double S[78];
+#pragma unroll
+    for (int i = 0; i < 78; i++) S[i] = 0.0;
+    const bool has_l = R.k > 0, has_r = R.k < a.n_seps;
+    if (has_l) {
+        const double* cr = a.covred + ((int64_t)(R.k - 1) * kCovRedDoubles) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < 21; i++) S[i] = cr[(int64_t)i * a.P];
+        if (has_r) {
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+#pragma unroll
+                for (int u = 0; u < 6; u++) S[tri(6 + i, u)] = cr[(int64_t)(21 + 6 * u + i) * a.P];
+        }
+    }
+    if (has_r) {
+        const double* cr = a.covred + ((int64_t)R.k * kCovRedDoubles) * a.P + p;
+#pragma unroll
+        for (int i = 0; i < 6; i++)
+#pragma unroll
+            for (int u = 0; u <= i; u++) S[tri(6 + i, 6 + u)] = cr[(int64_t)tri(i, u) * a.P];
+    }
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        const int t = R.g0 + R.n + q;
+        if (t < R.hi) {
+            const int o = 6 + 3 * q;
+            put_cov(a, t, p, S[tri(o, o)], S[tri(o + 1, o)], S[tri(o + 2, o)], S[tri(o + 1, o + 1)], S[tri(o + 2, o + 1)],
+                    S[tri(o + 2, o + 2)]);
+            if (q == 0 || t == a.T - 1) {
+                double c[9];
+#pragma unroll
+                for (int r = 0; r < 3; r++)
+#pragma unroll
+                    for (int u = 0; u < 3; u++) c[3 * r + u] = S[tri(9 + u, 6 + r)];
+                put_cross(a, t, p, c);
+            }
+        }
+    }
+    // the factor and the pivot of step i-1 are requested while step i is worked on
+    double G[36], Pi[kPivDoubles], Gn[36], Pn[kPivDoubles];
+    {
+        const double* f = a.fac + fac_index(a, R.n - 1, lane);
+        const double* pv = a.piv + piv_index(a, R.n - 1, lane);
+#pragma unroll
+        for (int k = 0; k < 36; k++) G[k] = f[k * kSmBlock];
+#pragma unroll
+        for (int k = 0; k < kPivDoubles; k++) Pi[k] = pv[k * kSmBlock];
+    }
+    for (int i = R.n - 1; i >= 0; i--) {
+        if (i > 0) {
+            const double* f = a.fac + fac_index(a, i - 1, lane);
+            const double* pv = a.piv + piv_index(a, i - 1, lane);
+#pragma unroll
+            for (int k = 0; k < 36; k++) Gn[k] = f[k * kSmBlock];
+#pragma unroll
+            for (int k = 0; k < kPivDoubles; k++) Pn[k] = pv[k * kSmBlock];
+        }
+        // V = Σ_N,N G  (= −Σ_N,a)
+        double V[36];
+#pragma unroll
+        for (int o = 0; o < 12; o++)
+#pragma unroll
+            for (int d = 0; d < 3; d++) {
+                double v = 0.0;
+#pragma unroll
+                for (int u = 0; u < 12; u++) v += S[sym(o, u)] * G[3 * u + d];
+                V[3 * o + d] = v;
+            }
+        double Saa[6];
+#pragma unroll
+        for (int d = 0; d < 3; d++)
+#pragma unroll
+            for (int e = 0; e <= d; e++) {
+                double v = Pi[sym3(d, e)];
+#pragma unroll
+                for (int o = 0; o < 12; o++) v += G[3 * o + d] * V[3 * o + e];
+                Saa[sym3(d, e)] = v;
+            }
+        const int t = R.g0 + i;
+        put_cov(a, t, p, Saa[0], Saa[1], Saa[2], Saa[3], Saa[4], Saa[5]);
+        {
+            double c[9];
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int u = 0; u < 3; u++) c[3 * r + u] = -V[3 * (6 + u) + r];
+            put_cross(a, t, p, c);
+        }
+        if (i == 0 && has_l) {
+            double c[9];
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+#pragma unroll
+                for (int u = 0; u < 3; u++) c[3 * r + u] = -V[3 * (3 + r) + u];
+            put_cross(a, t - 1, p, c);
+        }
+        // the window shifts to (L, a, b): rows 6..8 move to 9..11, frame a takes 6..8
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+#pragma unroll
+            for (int u = 0; u < 6; u++) S[tri(9 + d, u)] = S[tri(6 + d, u)];
+#pragma unroll
+            for (int e = 0; e <= d; e++) S[tri(9 + d, 9 + e)] = S[tri(6 + d, 6 + e)];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+#pragma unroll
+            for (int u = 0; u < 6; u++) S[tri(6 + d, u)] = -V[3 * u + d];
+#pragma unroll
+            for (int e = 0; e <= d; e++) S[tri(6 + d, 6 + e)] = Saa[sym3(d, e)];
+#pragma unroll
+            for (int e = 0; e < 3; e++) S[tri(9 + d, 6 + e)] = -V[3 * (6 + d) + e];
+        }
+        if (i > 0) {
+#pragma unroll
+            for (int k = 0; k < 36; k++) G[k] = Gn[k];
+#pragma unroll
+            for (int k = 0; k < kPivDoubles; k++) Pi[k] = Pn[k];
+        }
+    }
+}
+
 // ----------------------------------------------------------------- host side
 struct SmoothPlan {
     int chunk, n_chunks, n_seps, steps;
@@ -513,6 +802,22 @@ inline SmoothPlan smooth_plan(const char* fn, int T, int P, int chunk) {
     b = align256(b + (int64_t)P * 4);
     pl.bytes = b;
     return pl;
+}
+
+// What a covariance call adds behind `base` bytes of its solver's workspace.
+struct CovPlan {
+    int64_t off_piv, off_covred, bytes;
+};
+
+inline CovPlan cov_plan(const SmoothPlan& sp, int P, int64_t base) {
+    CovPlan cp;
+    int64_t b = base;
+    cp.off_piv = b;
+    b = align256(b + (int64_t)sp.steps * sp.n_blocks * kPivDoubles * kSmBlock * 8);
+    cp.off_covred = b;
+    b = align256(b + (int64_t)sp.n_seps * kCovRedDoubles * P * 8);
+    cp.bytes = b;
+    return cp;
 }
 
 }  // namespace

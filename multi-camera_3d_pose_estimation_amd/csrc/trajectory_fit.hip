@@ -31,7 +31,11 @@
 // output.  A per-chain flag in the workspace makes a finished chain's lanes return at once, and a
 // chain whose last trial was rejected keeps its linearisation.  Nothing is decided on the host.
 //
-// Register / LDS / scratch figures and the measurements are in DESIGN.md §4.14.
+// mvp_trajectory_fit_cov enqueues prepare, sum, decide(0) (the validity pass, at the given state),
+// terms<JAC> at that state, then eliminate with no Marquardt factor and the pivots kept, reduce with
+// the reduced system's selected inverse behind it, and the covariance sweep of smooth_solver.h.
+//
+// Register / LDS / scratch figures and the measurements are in DESIGN.md §4.14 and §4.16.
 #include "trajectory_fit_terms.h"
 
 namespace {
@@ -279,6 +283,26 @@ __global__ __launch_bounds__(kSmBlock) void fit_backsub_kernel(FitSolveArgs a) {
     if (lane < a.n_lanes) backsub_lane(a, lane);
 }
 
+// mvp_trajectory_fit_cov: the solver's sweeps over the undamped linearisation at a given state,
+// then the covariance sweep of smooth_solver.h where the fit has its backsub.
+__global__ __launch_bounds__(kSmBlock) void fit_cov_eliminate_kernel(FitCovArgs a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) eliminate_lane(a, lane);
+}
+
+__global__ __launch_bounds__(kSmBlock) void fit_cov_reduce_kernel(FitCovArgs a) {
+    const int p = blockIdx.x * kSmBlock + threadIdx.x;
+    if (p < a.P) {
+        reduce_chain(a, p);
+        reduce_cov_chain(a, p);
+    }
+}
+
+__global__ __launch_bounds__(kSmBlock) void fit_cov_kernel(FitCovArgs a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) cov_lane(a, lane);
+}
+
 // ------------------------------------------------------------------------------- output
 __global__ __launch_bounds__(kBlock) void fit_output_kernel(FitObs o, const float* __restrict__ xyz0,
                                                             const double* __restrict__ x64, FitChain ch,
@@ -355,6 +379,96 @@ extern "C" int mvp_trajectory_fit_system(const float* kpts, int T, int P, int V,
     hipLaunchKernelGGL(fit_terms_kernel<true>, dim3(tri_grid(fn, (int64_t)T * P)), dim3(kBlock), 0, s, a);
     MVP_HIP(hipGetLastError());
     hipLaunchKernelGGL(fit_system_cost_kernel, dim3((unsigned)P), dim3(kBlock), 0, s, o, xyz, out_cost);
+    MVP_HIP(hipGetLastError());
+    MVP_ABI_END
+}
+
+extern "C" int mvp_trajectory_fit_cov_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks,
+                                           int64_t* workspace_bytes) {
+    MVP_ABI_BEGIN
+    const FitPlan pl = fit_plan("mvp_trajectory_fit_cov_plan", T, P, chunk);
+    const CovPlan cp = cov_plan(pl.sp, P, pl.bytes);
+    if (chunk_used) *chunk_used = pl.sp.chunk;
+    if (n_chunks) *n_chunks = pl.sp.n_chunks;
+    if (workspace_bytes) *workspace_bytes = cp.bytes;
+    MVP_ABI_END
+}
+
+// prepare, sum, decide(0): the fit's validity pass at xyz; terms<JAC> at xyz: H̃; then eliminate
+// (no Marquardt factor, pivots kept), reduce + its selected inverse, and the covariance sweep.
+extern "C" int mvp_trajectory_fit_cov(const float* kpts, int T, int P, int V, const double* cams, int n_cams,
+                                      const int* cam_idx, int n_cam_idx, const float* xyz, const uint8_t* mask,
+                                      int weights, const double* gauss, float min_conf, float cov_floor,
+                                      double huber_delta, double lambda_smooth, int chunk, void* workspace,
+                                      int64_t workspace_bytes, float* out_cov, float* out_cross, uint8_t* out_status,
+                                      void* stream) {
+    MVP_ABI_BEGIN
+    const char* fn = "mvp_trajectory_fit_cov";
+    const FitObs o = fit_parse(fn, kpts, T, P, V, cams, n_cams, cam_idx, n_cam_idx, mask, weights, gauss, min_conf,
+                               cov_floor, huber_delta);
+    const FitPlan pl = fit_plan(fn, T, P, chunk);
+    const CovPlan cp = cov_plan(pl.sp, P, pl.bytes);
+    MVP_REQUIRE(std::isfinite(lambda_smooth) && lambda_smooth > 0, "%s: lambda_smooth=%g must be finite and > 0", fn,
+                lambda_smooth);
+    MVP_REQUIRE(workspace_bytes >= cp.bytes, "%s: workspace_bytes=%lld < %lld needed (T=%d, P=%d, chunk=%d)", fn,
+                (long long)workspace_bytes, (long long)cp.bytes, T, P, pl.sp.chunk);
+    MVP_REQUIRE(kpts && cams && xyz && workspace && out_cov, "%s: null device pointer", fn);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    FitChain ch;
+    {
+        char* c = ws + pl.off_chain;
+        ch.mu = reinterpret_cast<double*>(c);
+        ch.f = ch.mu + P;
+        ch.fseed = ch.f + P;
+        ch.cur = reinterpret_cast<int*>(ch.fseed + P);
+        ch.done = ch.cur + P;
+        ch.status = ch.done + P;
+        ch.relin = ch.status + P;
+        ch.rej = ch.relin + P;
+    }
+    double* x64 = reinterpret_cast<double*>(ws + pl.off_x);
+    double* c2 = reinterpret_cast<double*>(ws + pl.off_c2);
+    double* part = reinterpret_cast<double*>(ws + pl.off_part);
+    FitCovArgs a{};
+    a.T = T, a.P = P, a.chunk = pl.sp.chunk, a.n_chunks = pl.sp.n_chunks, a.n_seps = pl.sp.n_seps;
+    a.n_lanes = pl.sp.n_lanes, a.n_blocks = pl.sp.n_blocks;
+    a.lambda = lambda_smooth;
+    a.fac = reinterpret_cast<double*>(ws + pl.sp.off_fac);
+    a.schur = reinterpret_cast<double*>(ws + pl.sp.off_schur);
+    a.red = reinterpret_cast<double*>(ws + pl.sp.off_red);
+    a.usol = reinterpret_cast<double*>(ws + pl.sp.off_usol);
+    a.cnt = reinterpret_cast<int*>(ws + pl.sp.off_cnt);
+    a.bad = reinterpret_cast<int*>(ws + pl.sp.off_bad);
+    a.fail = reinterpret_cast<int*>(ws + pl.sp.off_fail);
+    a.piv = reinterpret_cast<double*>(ws + cp.off_piv);
+    a.covred = reinterpret_cast<double*>(ws + cp.off_covred);
+    a.H = reinterpret_cast<double*>(ws + pl.off_H);
+    a.g = reinterpret_cast<double*>(ws + pl.off_g);
+    a.invalid = ch.done;
+    a.out_cov = out_cov;
+    a.out_cross = out_cross;
+    a.out_status = out_status;
+    FitTerms ta{};
+    ta.o = o;
+    ta.x32 = xyz;   // the given state itself: no chain flag is read
+    ta.lambda = lambda_smooth;
+    ta.H = reinterpret_cast<double*>(ws + pl.off_H);
+    ta.g = reinterpret_cast<double*>(ws + pl.off_g);
+    const dim3 flat(tri_grid(fn, (int64_t)T * P)), blk(kBlock);
+    const dim3 chain_grid((unsigned)((P + kSmBlock - 1) / kSmBlock)), lane_grid((unsigned)pl.sp.n_blocks), sm_blk(kSmBlock);
+    MVP_HIP(hipMemsetAsync(a.cnt, 0, (size_t)P * 8, s));
+    hipLaunchKernelGGL(fit_prepare_kernel, flat, blk, 0, s, o, xyz, x64, c2);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fit_sum_kernel, dim3((unsigned)pl.sum_blocks), dim3(kFitRows * 64), 0, s, c2, T, P,
+                       (const int*)nullptr, part);
+    hipLaunchKernelGGL(fit_decide_kernel, chain_grid, sm_blk, 0, s, ch, part, pl.n_tiles, P, 0, 0, 1.0, a.bad);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fit_terms_kernel<true>, flat, blk, 0, s, ta);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(fit_cov_eliminate_kernel, lane_grid, sm_blk, 0, s, a);
+    hipLaunchKernelGGL(fit_cov_reduce_kernel, chain_grid, sm_blk, 0, s, a);
+    hipLaunchKernelGGL(fit_cov_kernel, lane_grid, sm_blk, 0, s, a);
     MVP_HIP(hipGetLastError());
     MVP_ABI_END
 }

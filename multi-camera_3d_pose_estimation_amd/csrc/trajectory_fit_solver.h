@@ -1,7 +1,7 @@
 // The trajectory fit's side of the partition solver (smooth_solver.h): the per-chain state, the
 // frame source that reads the information-form buffer and writes the trial state, and the
 // workspace plan.  Apart from trajectory_fit.hip's kernels, so that a host program can run the
-// sweeps lane by lane (tools/solver_host_check.cpp) without compiling them.
+// sweeps lane by lane (tools/solver_host_check.cpp, tools/cov_host_check.cpp) without compiling them.
 #pragma once
 #include "smooth_solver.h"
 
@@ -74,6 +74,43 @@ struct FitSolveArgs : SolveCore {
         x64[3 * e + 1] = f.x[1] + d1;
         x64[3 * e + 2] = f.x[2] + d2;
     }
+};
+
+// The frames of mvp_trajectory_fit_cov: the same information-form buffer at a given state, no
+// Marquardt factor, the inverse pivots kept; reduce_cov_chain and cov_lane then give Σ = A⁻¹.
+struct FitCovArgs : SolveCore, CovCore {
+    const double* H;     // [T][P][6]
+    const double* g;     // [T][P][3] (the eliminate sweep carries a right-hand side; nothing reads its result)
+    const int* invalid;  // [P] the validity pass's verdict
+    int* fail;           // [P]
+    uint8_t* out_status; // [P] or null
+    using Raw = FitRaw;
+    static constexpr bool kInfoForm = true;
+    static constexpr bool kKeepPivot = true;
+    MVP_SMOOTH_HD NoDamp damp(int) const { return NoDamp{}; }
+    MVP_SMOOTH_HD bool skip(int) const { return false; }
+    MVP_SMOOTH_HD FitRaw load_raw(int t, int p) const {
+        const int64_t e = (int64_t)t * P + p;
+        FitRaw f;
+#pragma unroll
+        for (int k = 0; k < 6; k++) f.h[k] = H[6 * e + k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) f.b[k] = g[3 * e + k];
+        return f;
+    }
+    MVP_SMOOTH_HD bool frame_weight(const FitRaw& f, double (&W)[6], double (&z)[3]) const {
+#pragma unroll
+        for (int k = 0; k < 6; k++) W[k] = f.h[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) z[k] = f.b[k];
+        return false;
+    }
+    MVP_SMOOTH_HD void finish(int p, int, int bad_pivot) const {
+        const int failed = (invalid[p] || bad_pivot) ? 1 : 0;
+        fail[p] = failed;
+        if (out_status) out_status[p] = failed ? 0x80 : 0;
+    }
+    MVP_SMOOTH_HD bool failed(int p) const { return fail[p] != 0; }
 };
 
 struct FitPlan {

@@ -106,6 +106,9 @@ SIGNATURES = {
     "mvp_trajectory_smooth_plan": (c_int, [c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
     "mvp_trajectory_smooth": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_float, c_float, c_int,
                                       c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_trajectory_smooth_cov_plan": (c_int, [c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
+    "mvp_trajectory_smooth_cov": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_double, c_float, c_float,
+                                          c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_epipolar_lag_cost_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int), P(c_int64)]),
     "mvp_epipolar_lag_cost": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_int, c_float,
                                       c_float, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -134,6 +137,10 @@ SIGNATURES = {
                                    c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_double, c_int, c_double,
                                    c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p]),
+    "mvp_trajectory_fit_cov_plan": (c_int, [c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
+    "mvp_trajectory_fit_cov": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p,
+                                       c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_double, c_int,
+                                       c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_skeleton_fit_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
     "mvp_skeleton_fit_system": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p,
                                         c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_int, P(c_int), c_int,

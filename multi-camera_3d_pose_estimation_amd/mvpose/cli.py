@@ -12,7 +12,8 @@
   is saved when requested; ``SGD`` runs the one-launch GPU refinement with the
   ``SGD`` section of --refinement_params_yaml and saves ``kpts_3d_SGD.npy``;
   ``smooth`` (no reference counterpart) runs the covariance-weighted smoother with the
-  ``smooth`` section and saves ``kpts_3d_smooth.npy`` and ``kpts_3d_smooth_resid.npy``.
+  ``smooth`` section and saves ``kpts_3d_smooth.npy`` and ``kpts_3d_smooth_resid.npy``, and
+  with ``with_cov: true`` in that section ``kpts_3d_smooth_cov.npy``, (T, J, 3, 3).
 """
 from __future__ import annotations
 
@@ -282,6 +283,8 @@ def pose_refinement_main(argv=None):
         print(f"saving smoothed trajectory at {path}")
         np.save(path, smooth)
         np.save(os.path.join(args.save_path, "kpts_3d_smooth_resid.npy"), info["resid"])
+        if "cov" in info:   # with_cov: true in the smooth section
+            np.save(os.path.join(args.save_path, "kpts_3d_smooth_cov.npy"), info["cov"])
         outputs["smooth"] = path
         types.discard("smooth")
     if "skeleton_fit" in types:   # the 2D keypoints, the smoothness prior and the bone lengths, from the smoother's seed

@@ -244,6 +244,33 @@ def triangulate_points_f64(kpts: torch.Tensor, cams: torch.Tensor, return_xyzw: 
     return (out, xyzw) if return_xyzw else out
 
 
+def _smooth_inputs(xyz, cov, valid):
+    """The checks trajectory_smooth makes of (xyz, cov, valid): T, P, the (T, P, 6) covariance and the
+    uint8 mask (or None)."""
+    _require(xyz, torch.float32, "xyz")
+    if xyz.dim() != 3 or xyz.shape[2] != 3:
+        raise ValueError(f"xyz must be (T, P, 3), got {tuple(xyz.shape)}")
+    T, P = int(xyz.shape[0]), int(xyz.shape[1])
+    cov6 = None
+    if cov is not None:
+        if not isinstance(cov, torch.Tensor) or cov.dtype != torch.float32 or not cov.is_cuda:
+            raise TypeError("cov must be a float32 torch.Tensor on the GPU")
+        if tuple(cov.shape) == (T, P, 3, 3):
+            cov6 = cov.reshape(T, P, 9)[..., [0, 1, 2, 4, 5, 8]].contiguous()
+        elif tuple(cov.shape) == (T, P, 6):
+            cov6 = cov.contiguous()
+        else:
+            raise ValueError(f"cov must be {(T, P, 3, 3)} or {(T, P, 6)}, got {tuple(cov.shape)}")
+    v8 = None
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or not valid.is_cuda:
+            raise TypeError("valid must be a bool or uint8 torch.Tensor on the GPU")
+        if tuple(valid.shape) != (T, P):
+            raise ValueError(f"valid must be {(T, P)}, got {tuple(valid.shape)}")
+        v8 = valid.to(torch.uint8).contiguous()
+    return T, P, cov6, v8
+
+
 def trajectory_smooth_plan(T: int, P: int, chunk: int = 0):
     """What trajectory_smooth will use for (T, P, chunk) (mvp_trajectory_smooth_plan): the chunk
     length, the chunks per chain and the workspace bytes."""
@@ -270,27 +297,7 @@ def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid:
     0, or 0x80 for a chain with fewer than 2 observed frames, which returns its input).  An
     output switched off by its want_* flag comes back as None.  The workspace is a torch.empty on
     the call's stream, sized by trajectory_smooth_plan."""
-    _require(xyz, torch.float32, "xyz")
-    if xyz.dim() != 3 or xyz.shape[2] != 3:
-        raise ValueError(f"xyz must be (T, P, 3), got {tuple(xyz.shape)}")
-    T, P = int(xyz.shape[0]), int(xyz.shape[1])
-    cov6 = None
-    if cov is not None:
-        if not isinstance(cov, torch.Tensor) or cov.dtype != torch.float32 or not cov.is_cuda:
-            raise TypeError("cov must be a float32 torch.Tensor on the GPU")
-        if tuple(cov.shape) == (T, P, 3, 3):
-            cov6 = cov.reshape(T, P, 9)[..., [0, 1, 2, 4, 5, 8]].contiguous()
-        elif tuple(cov.shape) == (T, P, 6):
-            cov6 = cov.contiguous()
-        else:
-            raise ValueError(f"cov must be {(T, P, 3, 3)} or {(T, P, 6)}, got {tuple(cov.shape)}")
-    v8 = None
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8) or not valid.is_cuda:
-            raise TypeError("valid must be a bool or uint8 torch.Tensor on the GPU")
-        if tuple(valid.shape) != (T, P):
-            raise ValueError(f"valid must be {(T, P)}, got {tuple(valid.shape)}")
-        v8 = valid.to(torch.uint8).contiguous()
+    T, P, cov6, v8 = _smooth_inputs(xyz, cov, valid)
     _, _, nbytes = trajectory_smooth_plan(T, P, chunk)
     dev = xyz.device
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -303,6 +310,39 @@ def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid:
          float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(resid), opt(observed), opt(status),
          _stream(dev))
     return out, resid, observed.to(torch.bool) if observed is not None else None, status
+
+
+def trajectory_smooth_cov_plan(T: int, P: int, chunk: int = 0):
+    """What trajectory_smooth_cov will use for (T, P, chunk) (mvp_trajectory_smooth_cov_plan): the
+    chunk length, the chunks per chain and the workspace bytes."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_trajectory_smooth_cov_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
+         ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
+def trajectory_smooth_cov(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid: torch.Tensor | None = None, *,
+                          lambda_smooth: float = 1.0, sigma0: float = 1.0, cov_floor: float = 0.0, chunk: int = 0,
+                          want_cross: bool = True, want_status: bool = True):
+    """Posterior covariance of trajectory_smooth's result (mvp_trajectory_smooth_cov; stated in
+    include/mvpose.h): the blocks of Σ = A⁻¹, A the smoother's matrix for the same arguments.
+
+    Arguments as for trajectory_smooth; the coordinates count only through being finite.  Returns
+    (cov (T, P, 6) float32: (xx, xy, xz, yy, yz, zz) of Σ_{t,t}, for every frame, observed or not;
+    cross (T, P, 3, 3) float32: Σ_{t,t+1}, row = coordinate of X_t, NaN at t = T−1, or None without
+    want_cross; status (P,) uint8: 0, or 0x80 for a failed chain, whose blocks are all NaN), in world
+    units², all on the GPU.  Stream-ordered, no host synchronisation."""
+    T, P, cov6, v8 = _smooth_inputs(xyz, cov, valid)
+    _, _, nbytes = trajectory_smooth_cov_plan(T, P, chunk)
+    dev = xyz.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((T, P, 6), dtype=torch.float32, device=dev)
+    cross = torch.empty((T, P, 3, 3), dtype=torch.float32, device=dev) if want_cross else None
+    status = torch.empty((P,), dtype=torch.uint8, device=dev) if want_status else None
+    opt = (lambda t: _ptr(t) if t is not None else None)
+    call("mvp_trajectory_smooth_cov", _ptr(xyz), opt(cov6), opt(v8), T, P, float(lambda_smooth), float(sigma0),
+         float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(cross), opt(status), _stream(dev))
+    return out, cross, status
 
 
 def epipolar_lag_cost_plan(T: int, J: int, nv: int, max_lag: int):
@@ -633,6 +673,43 @@ def trajectory_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int
          float(lambda_smooth), int(max_iter), float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out),
          _ptr(resid), _ptr(nviews), _ptr(cost), _ptr(status), _stream(dev))
     return out, resid, nviews, cost, status
+
+
+def trajectory_fit_cov_plan(T: int, P: int, chunk: int = 0):
+    """What trajectory_fit_cov will use for (T, P, chunk) (mvp_trajectory_fit_cov_plan): the chunk
+    length, the chunks per chain and the workspace bytes."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call("mvp_trajectory_fit_cov_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
+         ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
+def trajectory_fit_cov(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz: torch.Tensor, *,
+                       weights: str = "conf", gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None,
+                       min_conf: float = 0.0, cov_floor: float = 1.0, huber_delta: float = 0.0,
+                       lambda_smooth: float = 1.0, chunk: int = 0, want_cross: bool = True):
+    """Covariance of a fitted trajectory (mvp_trajectory_fit_cov; stated in include/mvpose.h): the
+    blocks of Σ = (blockdiag(H̃) + lambda_smooth·D₂ᵀD₂ ⊗ I₃)⁻¹, H̃ trajectory_fit's linearisation at
+    xyz (T, P, 3) float32, normally trajectory_fit's output.  This is the Gauss-Newton / Laplace
+    covariance at that state.  Arguments as for trajectory_fit.
+
+    Returns (cov (T, P, 6) float32: (xx, xy, xz, yy, yz, zz) of Σ_{t,t}; cross (T, P, 3, 3) float32:
+    Σ_{t,t+1}, row = coordinate of X_t, NaN at t = T−1, or None without want_cross; status (P,)
+    uint8: 0, or 0x80 for an invalid chain, whose blocks are all NaN), in world units², all on the
+    GPU.  Stream-ordered, no host synchronisation."""
+    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    _, _, nbytes = trajectory_fit_cov_plan(T, P, chunk)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((T, P, 6), dtype=torch.float32, device=dev)
+    cross = torch.empty((T, P, 3, 3), dtype=torch.float32, device=dev) if want_cross else None
+    status = torch.empty((P,), dtype=torch.uint8, device=dev)
+    call("mvp_trajectory_fit_cov", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
+         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
+         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
+         float(lambda_smooth), int(chunk), _ptr(work), int(nbytes), _ptr(out),
+         _ptr(cross) if cross is not None else None, _ptr(status), _stream(dev))
+    return out, cross, status
 
 
 def skeleton_fit_plan(T: int, P: int, J: int, chunk: int = 0):

@@ -232,8 +232,13 @@ def gap_mask(observed, max_gap):
     return ~observed & ((nxt - last - 1) > int(max_gap))
 
 
+def _cov_full(c6):
+    """(..., 6) (xx, xy, xz, yy, yz, zz) -> (..., 3, 3)."""
+    return c6[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(c6.shape[:-1] + (3, 3))
+
+
 def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1.0, cov_floor=0.0, robust_k=None,
-                      robust_iters=3, max_gap=None, return_info=False, device=None):
+                      robust_iters=3, max_gap=None, return_info=False, device=None, with_cov=False):
     """Covariance-weighted smoothing of a whole recording with gap filling (mvp_trajectory_smooth,
     stated in include/mvpose.h; no reference counterpart).  points (T, P, 3); cov (T, P, 3, 3) or
     (T, P, 6), e.g. kpts_3d_cov.npy, or None (every frame then has covariance sigma0²·I); status
@@ -255,7 +260,12 @@ def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1
     max_gap: frames inside a run of unobserved frames longer than max_gap (leading and trailing
     runs count) are returned as NaN; the solve itself is unchanged.  None = no limit.
     return_info=True returns (points, {"resid" (T, P) float32, "observed" (T, P) bool, "status"
-    (P,) uint8})."""
+    (P,) uint8}).
+    with_cov=True adds to that info the posterior covariance of the result (mvp_trajectory_smooth_cov):
+    "cov" (T, P, 3, 3) float32, Σ_{t,t} of every frame, filled ones included, in the points' units²,
+    and "cov_next" (T, P, 3, 3) float32, Σ_{t,t+1} (row: coordinate of X_t; NaN in the last frame).
+    With robust_k it is the covariance of the final reweighted solve; frames that max_gap turns to
+    NaN get NaN covariance, and so does a joint that is returned as it came."""
     was_tensor = isinstance(points, torch.Tensor)
     x = points if was_tensor else torch.from_numpy(np.ascontiguousarray(np.asarray(points)))
     if x.dim() != 3 or x.shape[2] != 3:
@@ -280,12 +290,15 @@ def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1
         valid = (st.to(torch.int32) & 0x80) == 0
     kw = dict(lambda_smooth=lambda_smooth, sigma0=sigma0)
     diag = torch.tensor([1, 0, 0, 1, 0, 1], dtype=torch.float32, device=dev)
+    last_cov, last_floor = c6, cov_floor   # what the final solve weighs with
     if robust_k is None:
         out, resid, observed, st_out = ops.trajectory_smooth(x, c6, valid, cov_floor=cov_floor, **kw)
     else:
+        last_floor = 0.0
         if c6 is not None:   # the covariance the loop scales: cov + cov_floor·I, float32
             base = c6 + torch.tensor(float(cov_floor), dtype=torch.float32, device=dev) * diag
             out, resid, observed, st_out = ops.trajectory_smooth(x, base, valid, cov_floor=0.0, **kw)
+            last_cov = base
         else:
             s2 = torch.tensor(float(sigma0), dtype=torch.float32, device=dev) ** 2
             base = (s2 * diag).expand(T, P, 6)
@@ -295,16 +308,25 @@ def smooth_trajectory(points, cov=None, status=None, lambda_smooth=1.0, sigma0=1
         for _ in range(int(robust_iters)):
             d = torch.sqrt(resid * scale)
             scale = torch.where(d > k, d / k, torch.ones_like(d))     # NaN (unobserved) -> 1
-            out, resid, observed, st_out = ops.trajectory_smooth(x, (base * scale.unsqueeze(-1)).contiguous(), valid,
-                                                                 cov_floor=0.0, **kw)
+            last_cov = (base * scale.unsqueeze(-1)).contiguous()
+            out, resid, observed, st_out = ops.trajectory_smooth(x, last_cov, valid, cov_floor=0.0, **kw)
         resid = resid * scale
+    info = {"resid": resid, "observed": observed, "status": st_out}
+    if with_cov and return_info:
+        c, cn, _ = ops.trajectory_smooth_cov(x, last_cov, valid, cov_floor=last_floor, **kw)
+        info["cov"], info["cov_next"] = _cov_full(c), cn
     if max_gap is not None:
-        out = torch.where(gap_mask(observed, max_gap).unsqueeze(-1), torch.full_like(out, float("nan")), out)
+        gap = gap_mask(observed, max_gap)
+        out = torch.where(gap.unsqueeze(-1), torch.full_like(out, float("nan")), out)
+        if "cov" in info:
+            g4 = gap.reshape(T, P, 1, 1)
+            info["cov"] = torch.where(g4, torch.full_like(info["cov"], float("nan")), info["cov"])
+            g4 = g4 | torch.cat([gap[1:], torch.zeros_like(gap[:1])]).reshape(T, P, 1, 1)   # either frame of the pair
+            info["cov_next"] = torch.where(g4, torch.full_like(info["cov_next"], float("nan")), info["cov_next"])
     if was_tensor:
-        res, info = out.to(home), {"resid": resid.to(home), "observed": observed.to(home), "status": st_out.to(home)}
+        res, info = out.to(home), {n: v.to(home) for n, v in info.items()}
     else:
-        res = out.cpu().numpy()
-        info = {"resid": resid.cpu().numpy(), "observed": observed.cpu().numpy(), "status": st_out.cpu().numpy()}
+        res, info = out.cpu().numpy(), {n: v.cpu().numpy() for n, v in info.items()}
     return (res, info) if return_info else res
 
 
@@ -354,7 +376,7 @@ def _fit_inputs(kpts_2d, camera_params, seed, camera_indices, weights, gauss, ma
 
 def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="conf", gauss=None, mask=None,
                    lambda_smooth=1.0, huber_px=0.0, min_conf=0.0, cov_floor=1.0, max_iter=30, tol=1e-6, chunk=0,
-                   return_info=False, device=None):
+                   return_info=False, device=None, with_cov=False):
     """Trajectories fitted to the 2D keypoints, so that a frame seen by a single camera still counts
     (mvp_trajectory_fit, stated in include/mvpose.h; no reference counterpart: the reference's
     sgd_optimize scores the same pixels, in f32 with Adam, with no mask, no robust loss and no
@@ -384,7 +406,11 @@ def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="c
     returns (points, {"resid" (T, [Np,] J) float32: Σ over the used views of the whitened squared
     residual, NaN without a view; "nviews" uint8; "cost" ([Np,] J, 2) float64: at the seed and at the
     result; "status" ([Np,] J) uint8: bits 0-5 the trials, 0x40 not converged, 0x80 returned as it
-    came})."""
+    came}).  with_cov=True adds to that info the Gauss-Newton / Laplace covariance at the result
+    (mvp_trajectory_fit_cov): "cov" (T, [Np,] J, 3, 3) float32, Σ_{t,t} in world units², and
+    "cov_next", same shape, Σ_{t,t+1} (row: coordinate of X_t; NaN in the last frame); all NaN for a
+    joint that is returned as it came.  Over a stretch seen by one camera its large axis lies along
+    that camera's rays: it says which frames wander, and in which direction."""
     k, x0, idx, cams, g, m, lead, finish = _fit_inputs(kpts_2d, camera_params, seed, camera_indices, weights, gauss, mask,
                                                        device)
     out, resid, nviews, cost, status = ops.trajectory_fit(
@@ -392,6 +418,11 @@ def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="c
         huber_delta=huber_px, lambda_smooth=lambda_smooth, max_iter=max_iter, tol=tol, chunk=chunk)
     info = {"resid": resid.reshape(lead), "nviews": nviews.reshape(lead), "cost": cost.reshape(lead[1:] + (2,)),
             "status": status.reshape(lead[1:])}
+    if with_cov and return_info:
+        c, cn, _ = ops.trajectory_fit_cov(k, cams, idx, out, weights=weights, gauss=g, mask=m, min_conf=min_conf,
+                                          cov_floor=cov_floor, huber_delta=huber_px, lambda_smooth=lambda_smooth,
+                                          chunk=chunk)
+        info["cov"], info["cov_next"] = _cov_full(c).reshape(lead + (3, 3)), cn.reshape(lead + (3, 3))
     out = out.reshape(lead + (3,))
     out, info = finish(out, info)
     return (out, info) if return_info else out

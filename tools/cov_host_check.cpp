@@ -1,0 +1,185 @@
+// Drives the posterior-covariance sweeps (eliminate_lane with the pivots kept, reduce_chain,
+// reduce_cov_chain, cov_lane of csrc/smooth_solver.h over the frame source FitCovArgs of
+// csrc/trajectory_fit_solver.h) on the HOST, lane by lane, and compares the diagonal and lag-1
+// blocks they write with a dense inverse of the same matrix.  The per-lane functions compile for
+// the host, so this is where a sanitizer can watch their indexing:
+//
+//   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Iinclude -Imulti-camera_3d_pose_estimation_amd/csrc \
+//         -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//         tools/cov_host_check.cpp multi-camera_3d_pose_estimation_amd/csrc/abi.cpp \
+//         -o /tmp/cov_host_check && /tmp/cov_host_check
+//
+// No device call is made; the program needs no GPU.  Every output element must be written (the
+// buffers start as a sentinel) and lie within 2^-23 sqrt(Σii Σjj) of the dense inverse, the bound
+// of tests/test_trajectory_cov_gpu.py.
+#include "../multi-camera_3d_pose_estimation_amd/csrc/trajectory_fit_solver.h"
+
+#include <cstdio>
+#include <random>
+#include <vector>
+
+namespace {
+
+constexpr float kSentinel = -12345.f;
+
+// inv(A) of the dense SPD A (n x n, row-major) by Cholesky; false on a pivot that is not > 0.
+bool dense_inverse(std::vector<double> A, int n, std::vector<double>& inv) {
+    for (int j = 0; j < n; j++) {
+        double d = A[j * n + j];
+        for (int k = 0; k < j; k++) d -= A[j * n + k] * A[j * n + k];
+        if (!(d > 0)) return false;
+        const double l = std::sqrt(d);
+        A[j * n + j] = l;
+        for (int i = j + 1; i < n; i++) {
+            double v = A[i * n + j];
+            for (int k = 0; k < j; k++) v -= A[i * n + k] * A[j * n + k];
+            A[i * n + j] = v / l;
+        }
+    }
+    inv.assign((size_t)n * n, 0.0);
+    std::vector<double> b(n);
+    for (int c = 0; c < n; c++) {
+        for (int i = 0; i < n; i++) {
+            double v = i == c ? 1.0 : 0.0;
+            for (int k = c; k < i; k++) v -= A[i * n + k] * b[k];
+            b[i] = i < c ? 0.0 : v / A[i * n + i];
+        }
+        for (int i = n - 1; i >= 0; i--) {
+            double v = b[i];
+            for (int k = i + 1; k < n; k++) v -= A[k * n + i] * b[k];
+            b[i] = v / A[i * n + i];
+        }
+        for (int i = 0; i < n; i++) inv[(size_t)i * n + c] = b[i];
+    }
+    return true;
+}
+
+// The largest error over the bound (<= 1 passes); 1e30 on a structural failure.
+double check(int T, int P, int chunk, double lambda, unsigned seed) {
+    const FitPlan pl = fit_plan("cov_host_check", T, P, chunk);
+    const CovPlan cp = cov_plan(pl.sp, P, pl.bytes);
+    std::vector<char> ws((size_t)cp.bytes);   // exactly the plan's bytes: an index past them is an error
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> uni(-1.0, 1.0);
+    const int64_t n = (int64_t)T * P;
+    std::vector<double> H(6 * n), g(3 * n);
+    std::vector<int> invalid(P, 0);
+    for (int64_t e = 0; e < n; e++) {
+        // rank 3, rank 2 (one view) and empty frames in turn; the first two frames are full
+        // (by t + p: a chain that saw nothing after frame 1 is too ill-conditioned for the bound)
+        const int t = (int)(e / P), kind = t < 2 ? 0 : (int)((t + e % P) % 3);
+        double J[3][3];
+        for (auto& row : J)
+            for (double& v : row) v = uni(rng);
+        for (int r = kind == 0 ? 3 : kind == 1 ? 2 : 0; r < 3; r++) J[r][0] = J[r][1] = J[r][2] = 0.0;
+        const int ij[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+        for (int k = 0; k < 6; k++) {
+            double s = 0.0;
+            for (int r = 0; r < 3; r++) s += J[r][ij[k][0]] * J[r][ij[k][1]];
+            H[6 * e + k] = s;
+        }
+        for (int k = 0; k < 3; k++) g[3 * e + k] = uni(rng);
+    }
+    std::vector<float> cov(6 * n, kSentinel), cross(9 * n, kSentinel);
+    std::vector<uint8_t> status(P, 0xFF);
+    FitCovArgs a{};
+    a.T = T, a.P = P, a.chunk = pl.sp.chunk, a.n_chunks = pl.sp.n_chunks, a.n_seps = pl.sp.n_seps;
+    a.n_lanes = pl.sp.n_lanes, a.n_blocks = pl.sp.n_blocks, a.lambda = lambda;
+    a.fac = reinterpret_cast<double*>(ws.data() + pl.sp.off_fac);
+    a.schur = reinterpret_cast<double*>(ws.data() + pl.sp.off_schur);
+    a.red = reinterpret_cast<double*>(ws.data() + pl.sp.off_red);
+    a.usol = reinterpret_cast<double*>(ws.data() + pl.sp.off_usol);
+    a.cnt = reinterpret_cast<int*>(ws.data() + pl.sp.off_cnt);
+    a.bad = reinterpret_cast<int*>(ws.data() + pl.sp.off_bad);
+    a.fail = reinterpret_cast<int*>(ws.data() + pl.sp.off_fail);
+    a.piv = reinterpret_cast<double*>(ws.data() + cp.off_piv);
+    a.covred = reinterpret_cast<double*>(ws.data() + cp.off_covred);
+    for (int p = 0; p < P; p++) a.cnt[p] = a.bad[p] = 0;
+    a.H = H.data(), a.g = g.data(), a.invalid = invalid.data();
+    a.out_cov = cov.data(), a.out_cross = cross.data(), a.out_status = status.data();
+    for (int64_t lane = 0; lane < a.n_lanes; lane++) eliminate_lane(a, lane);
+    for (int p = 0; p < P; p++) {
+        reduce_chain(a, p);
+        reduce_cov_chain(a, p);
+    }
+    for (int64_t lane = 0; lane < a.n_lanes; lane++) cov_lane(a, lane);
+    double worst = 0.0;
+    const int k6[6][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 1}, {1, 2}, {2, 2}};
+    for (int p = 0; p < P; p++) {
+        const int m = 3 * T;
+        std::vector<double> A((size_t)m * m, 0.0), S;
+        for (int s = 2; s < T; s++) {
+            const double v[3] = {1.0, -2.0, 1.0};
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++)
+                    for (int d = 0; d < 3; d++) A[(3 * (s - 2 + i) + d) * m + 3 * (s - 2 + j) + d] += lambda * v[i] * v[j];
+        }
+        for (int t = 0; t < T; t++) {
+            const double* h = &H[6 * ((int64_t)t * P + p)];
+            const double full[3][3] = {{h[0], h[1], h[2]}, {h[1], h[3], h[4]}, {h[2], h[4], h[5]}};
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) A[(3 * t + i) * m + 3 * t + j] += full[i][j];
+        }
+        if (!dense_inverse(A, m, S) || status[p] != 0) {
+            std::printf("T=%d P=%d chunk=%d chain %d: failure (status 0x%02x)\n", T, P, chunk, p, status[p]);
+            return 1e30;
+        }
+        for (int t = 0; t < T; t++) {
+            const int64_t e = (int64_t)t * P + p;
+            for (int k = 0; k < 6; k++) {
+                const int i = 3 * t + k6[k][0], j = 3 * t + k6[k][1];
+                const double bound = std::ldexp(std::sqrt(S[(size_t)i * m + i] * S[(size_t)j * m + j]), -23);
+                worst = std::fmax(worst, std::fabs((double)cov[6 * e + k] - S[(size_t)i * m + j]) / bound);
+            }
+            for (int k = 0; k < 9; k++) {
+                const float got = cross[9 * e + k];
+                if (t == T - 1) {
+                    if (!std::isnan(got)) return 1e30;
+                    continue;
+                }
+                const int i = 3 * t + k / 3, j = 3 * (t + 1) + k % 3;
+                const double bound = std::ldexp(std::sqrt(S[(size_t)i * m + i] * S[(size_t)j * m + j]), -23);
+                worst = std::fmax(worst, std::fabs((double)got - S[(size_t)i * m + j]) / bound);
+            }
+        }
+    }
+    // a chain the validity pass refused: all NaN, 0x80, every element written
+    invalid[0] = 1;
+    std::fill(cov.begin(), cov.end(), kSentinel);
+    std::fill(cross.begin(), cross.end(), kSentinel);
+    for (int p = 0; p < P; p++) a.cnt[p] = a.bad[p] = 0;
+    for (int64_t lane = 0; lane < a.n_lanes; lane++) eliminate_lane(a, lane);
+    for (int p = 0; p < P; p++) {
+        reduce_chain(a, p);
+        reduce_cov_chain(a, p);
+    }
+    for (int64_t lane = 0; lane < a.n_lanes; lane++) cov_lane(a, lane);
+    if (status[0] != 0x80) return 1e30;
+    for (int t = 0; t < T; t++)
+        for (int p = 0; p < P; p++) {
+            const int64_t e = (int64_t)t * P + p;
+            for (int k = 0; k < 6; k++)
+                if (cov[6 * e + k] == kSentinel || (p == 0) != (bool)std::isnan(cov[6 * e + k])) return 1e30;
+            for (int k = 0; k < 9; k++)
+                if (cross[9 * e + k] == kSentinel || (p == 0 || t == T - 1) != (bool)std::isnan(cross[9 * e + k])) return 1e30;
+        }
+    return worst;
+}
+
+}  // namespace
+
+int main() {
+    const int Ts[] = {1, 2, 3, 4, 5, 6, 7, 8, 11, 12, 13, 23, 40, 200};
+    double worst = 0.0;
+    for (int T : Ts)
+        for (int chunk : {4, 32, 0})
+            for (int P : {1, 3, 65})
+                for (double lambda : {0.7, 1e4}) {
+                    if (P == 65 && T > 40) continue;   // the dense inverse of 65 long chains takes minutes
+                    const double w = check(T, P, chunk, lambda, 17u * T + P);
+                    std::printf("T=%d P=%d chunk=%d lambda=%g: largest error / bound %.3g\n", T, P, chunk, lambda, w);
+                    worst = std::fmax(worst, w);
+                }
+    std::printf("worst %.3g\n", worst);
+    return worst <= 1.0 ? 0 : 1;
+}
