@@ -73,10 +73,12 @@ def apply_op(spec: D.DetSpec, T: list, op, cand: torch.Tensor, device_weights: b
             wp = torch.from_numpy(spec.f32_weights[op.aux])[:cout].permute(0, 3, 1, 2)
         else:
             wp = wf[op.aux:op.aux + cp * c].view(cp, 1, 1, c)[:cout].permute(0, 3, 1, 2)
-        y = _act(F.conv2d(t, wp, fb[op.b_off + c:op.b_off + c + cout]), op.act)
+        y = F.conv2d(t, wp, fb[op.b_off + c:op.b_off + c + cout])
+        if op.act == D.ACT_SILU:  # as DET_CONV: SiLU before the residual, ReLU after it
+            y = _act(y, op.act)
         if op.res.t >= 0:
             y = y + get(op.res)
-        put(op.out, y)
+        put(op.out, y if op.act == D.ACT_SILU else _act(y, op.act))
     elif op.kind == D.DET_CA:
         c = op.in_.c
         x = get(op.in_)
