@@ -35,9 +35,10 @@
 // (input frame, factor) one step ahead.  FMA contraction is allowed (no bit contract).
 // Register / LDS / scratch figures and the measurements are in DESIGN.md.
 //
-// The three sweeps' per-lane code and the plan are in smooth_solver.h, templated on the frame
-// source (the trajectory fit runs them over an information-form buffer); here: the smoother's
-// source, (xyz, cov, valid) -> (W, z) and the outputs, its kernels and the C entry points.
+// The three sweeps' per-lane code, their kernels (solve_eliminate_kernel<A>, solve_reduce_kernel<A>,
+// solve_backsub_kernel<A>) and the plan are in smooth_solver.h, templated on the frame source A (the
+// trajectory fit runs them over an information-form buffer); here: the smoother's sources,
+// (xyz, cov, valid) -> (W, z) and the outputs, and the C entry points.
 //
 // mvp_trajectory_smooth_cov runs the same eliminate and reduce over the same frames with the
 // inverse pivots kept, the reduced system's selected inverse behind the reduce, and the covariance
@@ -196,37 +197,18 @@ struct SmoothCovArgs : SmoothSrc, CovCore {
     MVP_SMOOTH_HD bool failed(int p) const { return fail[p] != 0; }
 };
 
-__global__ __launch_bounds__(kSmBlock) void smooth_cov_eliminate_kernel(SmoothCovArgs a) {
-    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
-    if (lane < a.n_lanes) eliminate_lane(a, lane);
-}
-
-__global__ __launch_bounds__(kSmBlock) void smooth_cov_reduce_kernel(SmoothCovArgs a) {
-    const int p = blockIdx.x * kSmBlock + threadIdx.x;
-    if (p < a.P) {
-        reduce_chain(a, p);
-        reduce_cov_chain(a, p);
-    }
-}
-
-__global__ __launch_bounds__(kSmBlock) void smooth_cov_kernel(SmoothCovArgs a) {
-    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
-    if (lane < a.n_lanes) cov_lane(a, lane);
-}
-
-__global__ __launch_bounds__(kSmBlock) void smooth_eliminate_kernel(SmoothArgs a) {
-    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
-    if (lane < a.n_lanes) eliminate_lane(a, lane);
-}
-
-__global__ __launch_bounds__(kSmBlock) void smooth_reduce_kernel(SmoothArgs a) {
-    const int p = blockIdx.x * kSmBlock + threadIdx.x;
-    if (p < a.P) reduce_chain(a, p);
-}
-
-__global__ __launch_bounds__(kSmBlock) void smooth_backsub_kernel(SmoothArgs a) {
-    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
-    if (lane < a.n_lanes) backsub_lane(a, lane);
+// The three launches of smooth_solver.h over a bound source, the counts the eliminate lanes add up
+// zeroed first.
+template <class A>
+void launch_solve(const A& a, hipStream_t s) {
+    const dim3 lane_grid((unsigned)a.n_blocks), chain_grid((unsigned)((a.P + kSmBlock - 1) / kSmBlock)), blk(kSmBlock);
+    MVP_HIP(hipMemsetAsync(a.cnt, 0, (size_t)a.P * 8, s));
+    hipLaunchKernelGGL(solve_eliminate_kernel<A>, lane_grid, blk, 0, s, a);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(solve_reduce_kernel<A>, chain_grid, blk, 0, s, a);
+    MVP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(solve_backsub_kernel<A>, lane_grid, blk, 0, s, a);
+    MVP_HIP(hipGetLastError());
 }
 
 }  // namespace
@@ -261,35 +243,14 @@ extern "C" int mvp_trajectory_smooth(const float* xyz, const float* cov, const u
     a.xyz = xyz;
     a.cov = cov;
     a.valid = valid;
-    a.T = T;
-    a.P = P;
-    a.chunk = pl.chunk;
-    a.n_chunks = pl.n_chunks;
-    a.n_seps = pl.n_seps;
-    a.n_lanes = pl.n_lanes;
-    a.n_blocks = pl.n_blocks;
-    a.lambda = lambda_smooth;
+    bind_core(a, ws, pl, T, P, lambda_smooth);
     a.w0 = 1.0 / ((double)sigma0 * (double)sigma0);
     a.cov_floor = (double)cov_floor;
-    a.fac = reinterpret_cast<double*>(ws + pl.off_fac);
-    a.schur = reinterpret_cast<double*>(ws + pl.off_schur);
-    a.red = reinterpret_cast<double*>(ws + pl.off_red);
-    a.usol = reinterpret_cast<double*>(ws + pl.off_usol);
-    a.cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
-    a.bad = reinterpret_cast<int*>(ws + pl.off_bad);
-    a.fail = reinterpret_cast<int*>(ws + pl.off_fail);
     a.out_xyz = out_xyz;
     a.out_resid = out_resid;
     a.out_observed = out_observed;
     a.out_status = out_status;
-    hipStream_t s = (hipStream_t)stream;
-    MVP_HIP(hipMemsetAsync(a.cnt, 0, (size_t)P * 8, s));
-    hipLaunchKernelGGL(smooth_eliminate_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(smooth_reduce_kernel, dim3((unsigned)((P + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(smooth_backsub_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
+    launch_solve(a, (hipStream_t)stream);
     MVP_ABI_END
 }
 
@@ -326,35 +287,11 @@ extern "C" int mvp_trajectory_smooth_cov(const float* xyz, const float* cov, con
     a.xyz = xyz;
     a.cov = cov;
     a.valid = valid;
-    a.T = T;
-    a.P = P;
-    a.chunk = pl.chunk;
-    a.n_chunks = pl.n_chunks;
-    a.n_seps = pl.n_seps;
-    a.n_lanes = pl.n_lanes;
-    a.n_blocks = pl.n_blocks;
-    a.lambda = lambda_smooth;
+    bind_core(a, ws, pl, T, P, lambda_smooth);
     a.w0 = 1.0 / ((double)sigma0 * (double)sigma0);
     a.cov_floor = (double)cov_floor;
-    a.fac = reinterpret_cast<double*>(ws + pl.off_fac);
-    a.schur = reinterpret_cast<double*>(ws + pl.off_schur);
-    a.red = reinterpret_cast<double*>(ws + pl.off_red);
-    a.usol = reinterpret_cast<double*>(ws + pl.off_usol);
-    a.cnt = reinterpret_cast<int*>(ws + pl.off_cnt);
-    a.bad = reinterpret_cast<int*>(ws + pl.off_bad);
-    a.fail = reinterpret_cast<int*>(ws + pl.off_fail);
     a.out_status = out_status;
-    a.piv = reinterpret_cast<double*>(ws + cp.off_piv);
-    a.covred = reinterpret_cast<double*>(ws + cp.off_covred);
-    a.out_cov = out_cov;
-    a.out_cross = out_cross;
-    hipStream_t s = (hipStream_t)stream;
-    MVP_HIP(hipMemsetAsync(a.cnt, 0, (size_t)P * 8, s));
-    hipLaunchKernelGGL(smooth_cov_eliminate_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(smooth_cov_reduce_kernel, dim3((unsigned)((P + kSmBlock - 1) / kSmBlock)), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
-    hipLaunchKernelGGL(smooth_cov_kernel, dim3((unsigned)pl.n_blocks), dim3(kSmBlock), 0, s, a);
-    MVP_HIP(hipGetLastError());
+    bind_cov(a, ws, cp, out_cov, out_cross);
+    launch_solve(a, (hipStream_t)stream);
     MVP_ABI_END
 }

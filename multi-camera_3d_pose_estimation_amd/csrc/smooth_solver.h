@@ -19,7 +19,10 @@
 // the diagonal and lag-1 blocks of A⁻¹.  Such a source needs failed(p) and none of the backsub
 // members.
 //
-// The per-lane functions also compile for the host, where a CPU build can step through them.
+// The three kernels of a source are solve_eliminate_kernel<A>, solve_reduce_kernel<A> and
+// solve_backsub_kernel<A> (below the per-lane code); bind_core fills a source's SolveCore fields
+// from the plan.  The per-lane functions also compile for the host, where a CPU build can step
+// through them.
 #pragma once
 // FMA contraction is allowed in everything below, whatever an earlier header left in force
 // (refine_common.h turns it off at file scope).
@@ -29,6 +32,7 @@
 #include <cmath>
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 
 #define MVP_SMOOTH_HD __host__ __device__ __forceinline__
 
@@ -754,6 +758,36 @@ MVP_SMOOTH_HD void cov_lane(const A& a, int64_t lane) {
     }
 }
 
+// ----------------------------------------------------------------- kernels
+// The three launches of a source A: one lane per (chain, chunk), per chain, per (chain, chunk).  A
+// source that keeps its pivots has the reduced system's selected inverse behind its reduce and the
+// covariance sweep for its third launch.
+template <class A>
+__global__ __launch_bounds__(kSmBlock) void solve_eliminate_kernel(A a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) eliminate_lane(a, lane);
+}
+
+template <class A>
+__global__ __launch_bounds__(kSmBlock) void solve_reduce_kernel(A a) {
+    const int p = blockIdx.x * kSmBlock + threadIdx.x;
+    if (p < a.P) {
+        reduce_chain(a, p);
+        if constexpr (keeps_pivot<A>::value) reduce_cov_chain(a, p);
+    }
+}
+
+template <class A>
+__global__ __launch_bounds__(kSmBlock) void solve_backsub_kernel(A a) {
+    const int64_t lane = (int64_t)blockIdx.x * kSmBlock + threadIdx.x;
+    if (lane < a.n_lanes) {
+        if constexpr (keeps_pivot<A>::value)
+            cov_lane(a, lane);
+        else
+            backsub_lane(a, lane);
+    }
+}
+
 // ----------------------------------------------------------------- host side
 struct SmoothPlan {
     int chunk, n_chunks, n_seps, steps;
@@ -818,6 +852,35 @@ inline CovPlan cov_plan(const SmoothPlan& sp, int P, int64_t base) {
     b = align256(b + (int64_t)sp.n_seps * kCovRedDoubles * P * 8);
     cp.bytes = b;
     return cp;
+}
+
+template <class A, class = void>
+struct has_fail : std::false_type {};
+template <class A>
+struct has_fail<A, std::void_t<decltype(std::declval<A&>().fail)>> : std::true_type {};
+
+// The fields of SolveCore in a source, over the workspace ws of plan sp; with them the source's
+// fail, where it has one.
+template <class A>
+inline void bind_core(A& a, char* ws, const SmoothPlan& sp, int T, int P, double lambda) {
+    a.T = T, a.P = P, a.chunk = sp.chunk, a.n_chunks = sp.n_chunks, a.n_seps = sp.n_seps;
+    a.n_lanes = sp.n_lanes, a.n_blocks = sp.n_blocks;
+    a.lambda = lambda;
+    a.fac = reinterpret_cast<double*>(ws + sp.off_fac);
+    a.schur = reinterpret_cast<double*>(ws + sp.off_schur);
+    a.red = reinterpret_cast<double*>(ws + sp.off_red);
+    a.usol = reinterpret_cast<double*>(ws + sp.off_usol);
+    a.cnt = reinterpret_cast<int*>(ws + sp.off_cnt);
+    a.bad = reinterpret_cast<int*>(ws + sp.off_bad);
+    if constexpr (has_fail<A>::value) a.fail = reinterpret_cast<int*>(ws + sp.off_fail);
+}
+
+// What a covariance source adds, over the same workspace.
+inline void bind_cov(CovCore& a, char* ws, const CovPlan& cp, float* out_cov, float* out_cross) {
+    a.piv = reinterpret_cast<double*>(ws + cp.off_piv);
+    a.covred = reinterpret_cast<double*>(ws + cp.off_covred);
+    a.out_cov = out_cov;
+    a.out_cross = out_cross;
 }
 
 }  // namespace

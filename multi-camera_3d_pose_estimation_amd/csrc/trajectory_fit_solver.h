@@ -1,7 +1,8 @@
 // The trajectory fit's side of the partition solver (smooth_solver.h): the per-chain state, the
 // frame source that reads the information-form buffer and writes the trial state, and the
-// workspace plan.  Apart from trajectory_fit.hip's kernels, so that a host program can run the
-// sweeps lane by lane (tools/solver_host_check.cpp, tools/cov_host_check.cpp) without compiling them.
+// workspace plan of the trajectory fit and the skeleton fit with the carving of its chain block.
+// Apart from trajectory_fit_kernels.h, so that a host program can run the sweeps lane by lane
+// (tools/solver_host_check.cpp, tools/cov_host_check.cpp) without compiling the fit's kernels.
 #pragma once
 #include "smooth_solver.h"
 
@@ -113,14 +114,19 @@ struct FitCovArgs : SolveCore, CovCore {
     MVP_SMOOTH_HD bool failed(int p) const { return fail[p] != 0; }
 };
 
+// The workspace of a fit behind its solver's: the chains' state, the groups' where chains decide
+// together (G of them; the skeleton fit), the two state buffers, the linearisation, the frames'
+// n_costs cost terms and their sums per tile.
 struct FitPlan {
     SmoothPlan sp;
     int n_tiles;
     int64_t sum_blocks;   // the sum kernel's workgroups: frame tiles x tiles of 64 chains
-    int64_t off_chain, off_x, off_H, off_g, off_c2, off_part, bytes;
+    int64_t off_chain, off_group, off_x, off_H, off_g, off_cost, off_part, bytes;
 };
 
-inline FitPlan fit_plan(const char* fn, int T, int P, int chunk) {
+constexpr int64_t kFitGroupBytes = 5 * 8 + 2 * 4;   // per group: 5 doubles, 2 ints (skeleton_fit.hip's SkGroup)
+
+inline FitPlan fit_plan(const char* fn, int T, int P, int chunk, int n_costs = 2, int G = 0) {
     FitPlan pl;
     pl.sp = smooth_plan(fn, T, P, chunk);
     MVP_REQUIRE((int64_t)T * P < (1LL << 31), "%s: T·P=%lld must be < 2^31", fn, (long long)T * P);
@@ -131,18 +137,34 @@ inline FitPlan fit_plan(const char* fn, int T, int P, int chunk) {
     int64_t b = pl.sp.bytes;
     pl.off_chain = b;
     b = align256(b + (int64_t)P * (3 * 8 + 5 * 4));
+    pl.off_group = b;
+    b = align256(b + G * kFitGroupBytes);
     pl.off_x = b;
     b = align256(b + 2 * n * 3 * 8);
     pl.off_H = b;
     b = align256(b + n * 6 * 8);
     pl.off_g = b;
     b = align256(b + n * 3 * 8);
-    pl.off_c2 = b;
-    b = align256(b + n * 2 * 8);
+    pl.off_cost = b;
+    b = align256(b + n * n_costs * 8);
     pl.off_part = b;
-    b = align256(b + (int64_t)pl.n_tiles * P * 2 * 8);
+    b = align256(b + (int64_t)pl.n_tiles * P * n_costs * 8);
     pl.bytes = b;
     return pl;
+}
+
+// The chains' state in the plan's chain block c.
+inline FitChain bind_chain(char* c, int P) {
+    FitChain ch;
+    ch.mu = reinterpret_cast<double*>(c);
+    ch.f = ch.mu + P;
+    ch.fseed = ch.f + P;
+    ch.cur = reinterpret_cast<int*>(ch.fseed + P);
+    ch.done = ch.cur + P;
+    ch.status = ch.done + P;
+    ch.relin = ch.status + P;
+    ch.rej = ch.relin + P;
+    return ch;
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// The trajectory fit's data term, shared by trajectory_fit.hip and skeleton_fit.hip: the observation
+// The trajectory fit's data term, under the kernels of trajectory_fit_kernels.h: the observation
 // arguments, one frame's terms at a state, and the argument checks of the entry points.
 #pragma once
 #include "trajectory_fit_solver.h"

@@ -83,20 +83,11 @@ double check(int T, int P, int chunk, double lambda, unsigned seed) {
     std::vector<float> cov(6 * n, kSentinel), cross(9 * n, kSentinel);
     std::vector<uint8_t> status(P, 0xFF);
     FitCovArgs a{};
-    a.T = T, a.P = P, a.chunk = pl.sp.chunk, a.n_chunks = pl.sp.n_chunks, a.n_seps = pl.sp.n_seps;
-    a.n_lanes = pl.sp.n_lanes, a.n_blocks = pl.sp.n_blocks, a.lambda = lambda;
-    a.fac = reinterpret_cast<double*>(ws.data() + pl.sp.off_fac);
-    a.schur = reinterpret_cast<double*>(ws.data() + pl.sp.off_schur);
-    a.red = reinterpret_cast<double*>(ws.data() + pl.sp.off_red);
-    a.usol = reinterpret_cast<double*>(ws.data() + pl.sp.off_usol);
-    a.cnt = reinterpret_cast<int*>(ws.data() + pl.sp.off_cnt);
-    a.bad = reinterpret_cast<int*>(ws.data() + pl.sp.off_bad);
-    a.fail = reinterpret_cast<int*>(ws.data() + pl.sp.off_fail);
-    a.piv = reinterpret_cast<double*>(ws.data() + cp.off_piv);
-    a.covred = reinterpret_cast<double*>(ws.data() + cp.off_covred);
+    bind_core(a, ws.data(), pl.sp, T, P, lambda);
+    bind_cov(a, ws.data(), cp, cov.data(), cross.data());
     for (int p = 0; p < P; p++) a.cnt[p] = a.bad[p] = 0;
     a.H = H.data(), a.g = g.data(), a.invalid = invalid.data();
-    a.out_cov = cov.data(), a.out_cross = cross.data(), a.out_status = status.data();
+    a.out_status = status.data();
     for (int64_t lane = 0; lane < a.n_lanes; lane++) eliminate_lane(a, lane);
     for (int p = 0; p < P; p++) {
         reduce_chain(a, p);

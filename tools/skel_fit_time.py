@@ -1,8 +1,8 @@
 #!/usr/bin/env python
 """Times mvp_skeleton_fit on the GPU beside mvp_trajectory_fit from another build of the library.
 
-    python tools/skel_fit_time.py --parent-lib PATH/libmvpose.so [--T 100000] [--reps 3]
-                                  [--out profiles/skel_fit_time.txt]
+    python tools/skel_fit_time.py --parent-lib PATH/libmvpose.so [--same-call] [--this-lib PATH/libmvpose.so]
+                                  [--T 100000] [--reps 3] [--out profiles/skel_fit_time.txt]
 
 One person of 17 joints with the reference's 12 segments, (T, G, J) = (100 000, 1, 17), nv = 2 and 8
 listed views, confidence weights, lambda 1, beta 1.  A call is timed with max_iter = 0, 1, 2, 3 and a
@@ -11,7 +11,9 @@ tolerance no run reaches, so that the group runs every trial; the differences ar
 state).  mvp_trajectory_fit is timed the same way on the same inputs from --parent-lib, a build of
 the commit before the skeleton fit (it lacks the symbols mvpose._lib asks for, so both libraries
 are driven through plain ctypes, each in child processes of its own), alternating with this
-build's mvp_skeleton_fit, twice each.
+build's mvp_skeleton_fit, twice each.  With --same-call, for a --parent-lib that has both calls (a
+change that must leave their speed alone): mvp_trajectory_fit from the parent build and from this
+one alternating, twice each, then mvp_skeleton_fit likewise.
 
 Device events around `reps` back-to-back calls after a warm-up, median [min, max] of 5 windows.
 Needs a GPU: no fallback."""
@@ -103,6 +105,10 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "skel_fit_time.txt"))
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--same-call", action="store_true",
+                    help="time each of the two calls from both libraries (the parent build has the skeleton fit too)")
+    ap.add_argument("--this-lib", default=os.path.join(PKG, "mvpose", "libmvpose.so"),
+                    help="the library timed as this build (the parent's again: what the comparison shows of two equal builds)")
     ap.add_argument("--child", nargs=3, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
@@ -132,7 +138,7 @@ def main():
     rng = np.random.default_rng(2)
     seed = (truth + rng.normal(0.0, 1.0, truth.shape)).astype(np.float32)
     lengths = np.array([[np.linalg.norm(truth[0, b] - truth[0, a]) for a, b in pairs]], np.float32)
-    here = os.path.join(PKG, "mvpose", "libmvpose.so")
+    here = args.this_lib
     with tempfile.TemporaryDirectory() as tmp:
         for nv in (2, 8):
             cams = syn.make_rig(nv, seed=3)
@@ -143,7 +149,10 @@ def main():
             inputs = os.path.join(tmp, f"nv{nv}.npz")
             np.savez(inputs, kpts=kpts, cams=ops.pack_cameras(syn.reference_camera_params(cams)), seed=seed,
                      lengths=lengths, pairs=pairs, nv=nv)
-            for kind, lib in (("fit", args.parent_lib), ("skel", here)) * 2:
+            runs = (("fit", args.parent_lib), ("skel", here)) * 2
+            if args.same_call:
+                runs = tuple((kind, lib) for kind in ("fit", "skel") for lib in (args.parent_lib, here) * 2)
+            for kind, lib in runs:
                 r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", kind, lib, inputs, "--reps",
                                     str(args.reps)], capture_output=True, text=True, timeout=600)
                 if r.returncode != 0:
@@ -154,6 +163,9 @@ def main():
                     emit(f"# mvp_skeleton_fit beside the parent build's mvp_trajectory_fit, {j['device']}, device events, "
                          f"median [min max] of 5 windows of {args.reps} calls, us")
                 what = "mvp_trajectory_fit, parent build" if kind == "fit" else "mvp_skeleton_fit, this build  "
+                if args.same_call:
+                    what = (f"{'mvp_trajectory_fit' if kind == 'fit' else 'mvp_skeleton_fit  '}, "
+                            f"{'parent' if lib == args.parent_lib else 'this  '} build")
                 emit(f"T={T} G=1 J={J} n_seg={len(pairs)} nv={nv} {what}: max_iter=0 {fmt(t[0])}; 1 {fmt(t[1])}; 2 {fmt(t[2])}; "
                      f"3 {fmt(t[3])}; seed path {t[0][0]:.0f}; first trial {t[1][0] - t[0][0]:.0f}; a later trial "
                      f"{t[2][0] - t[1][0]:.0f} and {t[3][0] - t[2][0]:.0f}; status after 3 {j['status']}; workspace "

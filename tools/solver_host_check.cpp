@@ -51,9 +51,14 @@ double check(int T, int P, int chunk, double lambda, unsigned seed) {
     std::mt19937 rng(seed);
     std::uniform_real_distribution<double> uni(-1.0, 1.0);
     const int64_t n = (int64_t)T * P;
-    std::vector<double> H(6 * n), g(3 * n), x64(2 * 3 * n), mu(P);
-    std::vector<int> cur(P), done(P, 0), rej(P, 0);
-    for (int p = 0; p < P; p++) mu[p] = 1e-3 * (p + 1), cur[p] = p & 1;
+    std::vector<double> H(6 * n), g(3 * n), x64(2 * 3 * n);
+    // the chains' state and the solver's fields lie in the workspace, carved as the library carves them
+    FitSolveArgs sa{};
+    bind_core(sa, ws.data(), pl.sp, T, P, lambda);
+    sa.ch = bind_chain(ws.data() + pl.off_chain, P);
+    double* const mu = sa.ch.mu;
+    int *const cur = sa.ch.cur, *const rej = sa.ch.rej;
+    for (int p = 0; p < P; p++) mu[p] = 1e-3 * (p + 1), cur[p] = p & 1, sa.ch.done[p] = rej[p] = 0;
     for (int64_t e = 0; e < n; e++) {
         // rank 3, rank 2 (one view) and empty frames in turn; the first two frames are full
         const int t = (int)(e / P), kind = t < 2 ? 0 : (int)((e + t) % 3);
@@ -71,18 +76,8 @@ double check(int T, int P, int chunk, double lambda, unsigned seed) {
         for (int b = 0; b < 2; b++)
             for (int k = 0; k < 3; k++) x64[3 * (b * n + e) + k] = 100.0 * uni(rng);
     }
-    FitSolveArgs sa{};
-    sa.T = T, sa.P = P, sa.chunk = pl.sp.chunk, sa.n_chunks = pl.sp.n_chunks, sa.n_seps = pl.sp.n_seps;
-    sa.n_lanes = pl.sp.n_lanes, sa.n_blocks = pl.sp.n_blocks, sa.lambda = lambda;
-    sa.fac = reinterpret_cast<double*>(ws.data() + pl.sp.off_fac);
-    sa.schur = reinterpret_cast<double*>(ws.data() + pl.sp.off_schur);
-    sa.red = reinterpret_cast<double*>(ws.data() + pl.sp.off_red);
-    sa.usol = reinterpret_cast<double*>(ws.data() + pl.sp.off_usol);
-    sa.cnt = reinterpret_cast<int*>(ws.data() + pl.sp.off_cnt);
-    sa.bad = reinterpret_cast<int*>(ws.data() + pl.sp.off_bad);
     for (int p = 0; p < P; p++) sa.cnt[p] = sa.bad[p] = 0;
     sa.H = H.data(), sa.g = g.data(), sa.x64 = x64.data();
-    sa.ch.mu = mu.data(), sa.ch.cur = cur.data(), sa.ch.done = done.data(), sa.ch.rej = rej.data();
     const std::vector<double> before = x64;
     for (int64_t lane = 0; lane < sa.n_lanes; lane++) eliminate_lane(sa, lane);
     for (int p = 0; p < P; p++) reduce_chain(sa, p);
