@@ -294,15 +294,9 @@ void launch_basic_block_c32(const uint16_t* x, const uint16_t* w1, const float* 
     MVP_REQUIRE(basic_block_c32_supported(H, W), "basic block: unsupported plane %dx%d", H, W);
     if (N == 0) return;
     using C = BlockCfg<48>;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)basic_block_c32_kernel<48>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-        attr = true;
-    }
     BlockParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, H, (int)((long)N * (H / C::TH))};
     const int grid = std::min(p.n_tiles, cu_count());
-    hipLaunchKernelGGL(basic_block_c32_kernel<48>, dim3(grid), dim3(C::NT), C::LDS, s, p);
+    launch_lds<basic_block_c32_kernel<48>, C::LDS>(grid, C::NT, s, p);
     MVP_HIP(hipGetLastError());
 }
 

@@ -74,14 +74,6 @@ __device__ __forceinline__ void barrier() {
     asm volatile("" ::: "memory");
 }
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
 // x-ring swizzle: chunk c16 of pixel p sits at slot p * 32 + ((c16 & 16) | ((c16 & 15) ^ bn_swz(p))).
 // ds_read_b128 serves lanes {0-3, 12-15, 20-27} (and the complementary set) together: conv1's
 // fragment lanes (pixel px, 16-channel group g) and conv3's residual lanes then hit 16
@@ -243,19 +235,9 @@ __device__ __forceinline__ void c2_role(const BNParams& p, uint8_t* lds, int jw,
         }
         // accumulators start at the lane's 16 biases (couts 32gr + 16h ..), from LDS
         f32x16 acc[NF];
-        {
-            const float4* bq = reinterpret_cast<const float4*>(lds + BN::BOFF + (gr * 32 + 16 * h) * 4);
+        acc[0] = load_f32x16(reinterpret_cast<const float*>(lds + BN::BOFF + (gr * 32 + 16 * h) * 4));
 #pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float4 b4 = bq[q];
-                acc[0][4 * q] = b4.x;
-                acc[0][4 * q + 1] = b4.y;
-                acc[0][4 * q + 2] = b4.z;
-                acc[0][4 * q + 3] = b4.w;
-            }
-#pragma unroll
-            for (int t = 1; t < NF; t++) acc[t] = acc[0];
-        }
+        for (int t = 1; t < NF; t++) acc[t] = acc[0];
         bf16x8 fb[kPF + 1][NF];
         auto load = [&](auto Ss) {
             constexpr int st = Ss, c = st / 18, tap = (st % 18) >> 1, ks = st & 1;
@@ -278,12 +260,10 @@ __device__ __forceinline__ void c2_role(const BNParams& p, uint8_t* lds, int jw,
         // ReLU, bf16 -> conv2's output planes (lane: couts 32gr + 16h .. +15 of its pixel)
 #pragma unroll
         for (int t = 0; t < NF; t++) {
-            uint32_t o[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) o[e] = pack_bf16x2(relu1(acc[t][2 * e]), relu1(acc[t][2 * e + 1]));
+            const Row16 o = pack_row16(acc[t], true);
             uint8_t* d = lds + BN::T2OFF + (4 * gr + 2 * h) * BN::T2PL + fpp[t] * 16;
-            *reinterpret_cast<uint4*>(d) = uint4{o[0], o[1], o[2], o[3]};
-            *reinterpret_cast<uint4*>(d + BN::T2PL) = uint4{o[4], o[5], o[6], o[7]};
+            *reinterpret_cast<uint4*>(d) = o.lo;
+            *reinterpret_cast<uint4*>(d + BN::T2PL) = o.hi;
         }
     };
 
@@ -598,14 +578,8 @@ bool bneck_supported(int H, int W, int C, int M) {
 
 template <bool LEAD>
 void launch_bneck_t(const BNParams& p, hipStream_t s) {
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)bneck_kernel<LEAD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    BNT<LEAD>::LDS));
-        attr = true;
-    }
     const int grid = std::min(p.N, cu_count());
-    hipLaunchKernelGGL(bneck_kernel<LEAD>, dim3(grid), dim3(512), BNT<LEAD>::LDS, s, p);
+    launch_lds<bneck_kernel<LEAD>, BNT<LEAD>::LDS>(grid, 512, s, p);
     MVP_HIP(hipGetLastError());
 }
 

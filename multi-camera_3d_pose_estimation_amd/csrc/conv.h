@@ -5,6 +5,7 @@
 #include <cstdint>
 
 #include "kernel_select.h"
+#include "mvp_common.h"
 
 namespace mvp {
 
@@ -160,14 +161,14 @@ void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uin
                   uint16_t* y, int N, int H, int W, bool crop_ranges, hipStream_t s);
 
 // Transition1 (trans1.hip): t0 = relu(conv3x3/s1(x, w0) + b0) (256 -> 32) and t1 =
-// relu(conv3x3/s2(x, w1) + b1) (256 -> 64) from ONE pass over x [N][64][48][256];
-// w0 [32][3][3][256] and w1 [64][3][3][256] bf16 at element offsets w0_off / w1_off of wb.  trans1_supported is false for other
-// shapes.
+// relu(conv3x3/s2(x, w1) + b1) (256 -> 64) from ONE pass over x [N][64][48][256], or, planar,
+// [N][16][64][48][16] (BneckLaunch::planar); wimg is trans1_pack_weights' image of w0 and w1.
+// trans1_supported is false for other shapes.
 bool trans1_supported(int H, int W, int C, int cout0, int cout1);
-void launch_trans1(const uint16_t* x, const uint16_t* wb, int64_t w0_off, const float* b0, int64_t w1_off,
-                   const float* b1, uint16_t* y0, uint16_t* y1, int N, hipStream_t s,
-                   const uint16_t* wimg = nullptr, bool planar = false);
-// trans1's weight image (9 x 2 x 96 16-B slots per 16-channel chunk, 221,184 elements)
+void launch_trans1(const uint16_t* x, const uint16_t* wimg, const float* b0, const float* b1, uint16_t* y0,
+                   uint16_t* y1, int N, bool planar, hipStream_t s);
+// trans1's weight image (9 x 2 x 96 16-B slots per 16-channel chunk, 221,184 elements) of w0
+// [32][3][3][256] and w1 [64][3][3][256] bf16 at element offsets w0_off / w1_off of wb
 constexpr long kTrans1ImageElems = 16L * 9 * 2 * 96 * 8;
 void trans1_pack_weights(const uint16_t* wb, int64_t w0_off, int64_t w1_off, uint16_t* img, hipStream_t s);
 
@@ -177,7 +178,22 @@ void launch_fuse_sum(const uint16_t* const* in, const int* up, int n_in, uint16_
                      int C, int relu, hipStream_t s);
 
 // 64 KiB of device zeros (out-of-image DMA source), allocated on first use.
+constexpr int kZeroSlots = 4096;  // its 16-B slots
 const uint16_t* conv_zero_region();
+// 2 KiB nobody reads (64 lanes x 32 B): where the lanes of a tile past the batch store their rows.
+uint16_t* conv_sink_region();
+
+// Launch Kern with LDS bytes of dynamic LDS; the kernel's limit is raised to that before its
+// first launch (once per instantiation, i.e. per kernel).
+template <auto Kern, int LDS, typename... Args>
+void launch_lds(int grid, int threads, hipStream_t s, const Args&... args) {
+    static const bool attr = [] {
+        MVP_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+        return true;
+    }();
+    (void)attr;
+    hipLaunchKernelGGL(Kern, dim3(grid), dim3(threads), LDS, s, args...);
+}
 
 // Fused BasicBlock on 32 channels (block.hip):
 //   y = relu(conv3x3(relu(conv3x3(x, w1) + b1), w2) + b2 + x), all bf16 NHWC [N][H][W][32],

@@ -53,7 +53,6 @@ struct ConvParams {
     int wmode;  // WM_ONCE / WM_RESIDENT / WM_STREAM
 };
 
-constexpr int kZeroSlots = 4096;  // 16-B slots of the zero region (64 KiB)
 
 // Weight staging modes: one 32-channel chunk staged once (Cin = 32); every chunk
 // resident in LDS for the whole launch (fits); or a per-chunk double buffer.
@@ -408,7 +407,6 @@ const uint16_t* zero_page() {
     if (!g_zero) {
         MVP_HIP(hipMalloc(&g_zero, kZeroSlots * 16));
         MVP_HIP(hipMemset(g_zero, 0, kZeroSlots * 16));
-        MVP_HIP(hipMalloc(&g_sink, 64 * 16));
     }
     return g_zero;
 }
@@ -466,8 +464,8 @@ void launch_cfg(const ConvParams& p0, hipStream_t s) {
     MVP_REQUIRE(nt < (1L << 31), "conv: too many tiles");
     p.n_tiles = (int)nt;
     p.zero = zero_page();
-    p.sink = g_sink;
-    p.sinkf = reinterpret_cast<float*>(g_sink);
+    p.sink = conv_sink_region();
+    p.sinkf = reinterpret_cast<float*>(p.sink);
     const int n_chunks = p.Cin / 32;
     p.wmode = wmode_for<KS, S, BM, TH, TW, NB, NW>(n_chunks);
     // ring depth: maximise DMA items in flight per CU = resident workgroups x (depth - 1)
@@ -763,6 +761,11 @@ __global__ __launch_bounds__(256) void fuse_sum_n_kernel(FuseParams p) {
 }  // namespace
 
 const uint16_t* conv_zero_region() { return zero_page(); }
+
+uint16_t* conv_sink_region() {
+    if (!g_sink) MVP_HIP(hipMalloc(&g_sink, 64 * 32));
+    return g_sink;
+}
 
 void launch_conv_generic(const ConvLaunch& c, hipStream_t s) {
     MVP_REQUIRE(!c.x2, "conv: the generic kernel takes one input");

@@ -8,6 +8,7 @@
 
 #include "conv.h"
 #include "det.h"
+#include "mfma_tile.h"
 #include "mvp_common.h"
 
 namespace mvp {
@@ -16,6 +17,7 @@ namespace mvp {
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mfma_tile::static_for;  // ring slots as compile-time register indices
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf(uint32_t v16) { return __uint_as_float(v16 << 16); }
@@ -137,15 +139,6 @@ __device__ __forceinline__ float4 lds_read_f4_sync(const float* p) {
     float4 v;
     asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(a) : "memory");
     return v;
-}
-
-// f(integral_constant<int, i>) for i in [B, E): ring slots as compile-time register indices
-template <int B, int E, typename F>
-__device__ __forceinline__ void det_static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        det_static_for<B + 1, E>(f);
-    }
 }
 
 // glds16_det to an LDS byte offset, as asm the compiler does not track (the persistent halo kernel

@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void det_conv1x1_pers_kernel(GParams p) {
         wait_vm(0);
         __builtin_amdgcn_s_barrier();
     }
-    det_static_for<0, D>([&](auto J) {
+    static_for<0, D>([&](auto J) {
         if (J < S) issue(J);
     });
     wait_vm(OPS * (int)(std::min<long>(D, S) - 1));
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void det_conv1x1_pers_kernel(GParams p) {
         it++;
     };
     for (long g = 0; g < S; g += NBUF)
-        det_static_for<0, NBUF>([&](auto J) {
+        static_for<0, NBUF>([&](auto J) {
             if (g + J < S) step(g + J, J);
         });
 }

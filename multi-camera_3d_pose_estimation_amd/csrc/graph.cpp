@@ -810,8 +810,8 @@ extern "C" int mvp_graph_forward(void* handle, const void* input_dev, int batch,
         }
         case mvp::R_TWIN: {  // transition1: this 3x3/s1 conv and its 3x3/s2 sibling, one pass
             const mvp_op_desc& b = g->ops[L.twin];
-            mvp::launch_trans1(bf16(op.in[0]), g->wb, op.w_off, g->fb + op.b_off, b.w_off, g->fb + b.b_off,
-                               bf16(op.out), bf16(b.out), nb, s, L.w_img, L.planar);
+            mvp::launch_trans1(bf16(op.in[0]), L.w_img, g->fb + op.b_off, g->fb + b.b_off, bf16(op.out),
+                               bf16(b.out), nb, L.planar, s);
             break;
         }
         case mvp::R_SIBLINGS: {  // this 3x3/s2 conv and its siblings on the same input

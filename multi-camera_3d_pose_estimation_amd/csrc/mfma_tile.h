@@ -1,9 +1,20 @@
-// Shared device helpers of the 32x32x16-MFMA convolution kernels (tconv.hip,
-// tblock.hip, tblock64.hip): LDS-DMA, epilogue packing, the permuted-cout A rows
-// and the bank-conflict-free lane -> pixel maps of a 32-pixel B fragment.
+// Shared device helpers of the 32x32x16-MFMA convolution kernels (tconv.hip, tconv16.hip,
+// s2conv.hip, trans1.hip, tblock.hip, tblock32s.hip, tblock64.hip, stem2.hip, bneck.hip;
+// the detector kernels take static_for through det_common.h): LDS-DMA,
+// the folded-BN bias load, the epilogue row (residual, ReLU, bf16 packing) of a lane's 16
+// couts, the ring item's wait + barrier, static_for, the permuted-cout A rows and the
+// bank-conflict-free lane -> pixel maps of a 32-pixel B fragment.
+//
+// These kernels sit at the edge of their register budgets and of what the compiler's wait
+// insertion sees through, so a helper is used only where the machine code stays what it was
+// (tools/isa_compare.py, profiles/mfma_refactor_isa.txt).  Left in the kernels for that
+// reason: the two-deep tap pipeline (any function boundary around it changed register counts
+// in tconv, tconv16, s2conv and tblock), the stride-1 halo slot decode (+5 to +10 VGPRs in
+// tconv), and the `live ? ... : 0u` epilogues that write an LDS intermediate.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <type_traits>
 
 namespace mvp {
 namespace mfma_tile {
@@ -34,6 +45,79 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {  // RNE, v
 }
 __device__ __forceinline__ float lo_bf16(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float hi_bf16(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+
+// f(integral_constant<int, i>) for i in [B, E): loop indices as compile-time constants
+template <int B, int E, typename F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (B < E) {
+        f(std::integral_constant<int, B>{});
+        static_for<B + 1, E>(f);
+    }
+}
+
+// 16 consecutive floats (a lane's folded-BN biases) as an accumulator; global or LDS
+__device__ __forceinline__ f32x16 load_f32x16(const float* p) {
+    f32x16 v;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float4 q = reinterpret_cast<const float4*>(p)[j];
+        v[4 * j] = q.x;
+        v[4 * j + 1] = q.y;
+        v[4 * j + 2] = q.z;
+        v[4 * j + 3] = q.w;
+    }
+    return v;
+}
+
+// Epilogue of one accumulator: the lane's 16 consecutive couts (+ the residual's 16 bf16 in
+// ra | rb), optional ReLU, rounded to bf16 -- the row's two 16-B halves.
+struct Row16 {
+    uint4 lo, hi;
+};
+template <bool RES>
+__device__ __forceinline__ Row16 pack_row16_impl(const f32x16& acc, bool relu, uint4 ra, uint4 rb) {
+    uint32_t o[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        float v0 = acc[2 * e], v1 = acc[2 * e + 1];
+        if (RES) {
+            const uint4 rr = e < 4 ? ra : rb;
+            const uint32_t u = (e & 3) == 0 ? rr.x : (e & 3) == 1 ? rr.y : (e & 3) == 2 ? rr.z : rr.w;
+            v0 += lo_bf16(u);
+            v1 += hi_bf16(u);
+        }
+        if (relu) {
+            v0 = relu1(v0);
+            v1 = relu1(v1);
+        }
+        o[e] = pack_bf16x2(v0, v1);
+    }
+    return Row16{uint4{o[0], o[1], o[2], o[3]}, uint4{o[4], o[5], o[6], o[7]}};
+}
+__device__ __forceinline__ Row16 pack_row16(const f32x16& acc, bool relu) {
+    return pack_row16_impl<false>(acc, relu, uint4{}, uint4{});
+}
+__device__ __forceinline__ Row16 pack_row16(const f32x16& acc, bool relu, uint4 ra, uint4 rb) {
+    return pack_row16_impl<true>(acc, relu, ra, rb);
+}
+__device__ __forceinline__ void store_row16(uint16_t* yrow, const Row16& r) {
+    *reinterpret_cast<uint4*>(yrow) = r.lo;
+    *reinterpret_cast<uint4*>(yrow + 8) = r.hi;
+}
+
+// Top of a ring item: item k's DMA has landed -- younger than it are only the previous tile's
+// STORES epilogue stores, and those only on a tile's first item past the launch's first -- then
+// the barrier that publishes every wave's pieces and retires all reads of the other ring slot.
+template <int STORES>
+__device__ __forceinline__ void item_wait_barrier(int k, bool first) {
+    if (k == 0 || !first)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(STORES) : "memory");
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 // cout held by A row r of a 32-cout group: row 8j+4h+i -> cout 16h+4j+i, so that the
 // accumulator lane (column = pixel, k-half h) owns couts 16h .. 16h+15 in order

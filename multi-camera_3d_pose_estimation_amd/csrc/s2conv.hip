@@ -37,9 +37,7 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;  // 16-B slots of the shared zero region
-
-template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM, bool PM_ = false>
+template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM>
 struct SCfg {
     static constexpr int NW = 8, NT_THREADS = NW * 64;
     static constexpr int MG = BM / 32, PG = NW / MG;  // cout groups x pixel groups
@@ -51,11 +49,11 @@ struct SCfg {
     static constexpr int PH = HR * RS;                // slots per phase plane
     static constexpr int HS = NB * 4 * PH;            // halo pixels per item
     static constexpr int HT = 2 * HS;                 // halo slots per item
-    // PM (pixel-major halo): a pixel's two 16-B planes are adjacent slots (32 B contiguous per
-    // pixel in a DMA instruction, half the cache lines of plane-major) at the price of 2-way
-    // bank conflicts on the fragment reads (16 pixels x 32 B pitch); plane-major otherwise.
-    static constexpr bool PM = PM_;
-    static constexpr int QS = PM ? 1 : HS, PS = PM ? 2 : 1;  // slots between planes / pixels
+    // Pixel-major halo: a pixel's two 16-B planes are adjacent slots (32 B contiguous per pixel
+    // in a DMA instruction, half the cache lines of plane-major) at the price of 2-way bank
+    // conflicts on the fragment reads (16 pixels x 32 B pitch): +0.7 % frames/s over
+    // plane-major, round 2.
+    static constexpr int QS = 1, PS = 2;              // slots between planes / pixels
     static constexpr int WT = 9 * 2 * BM;             // weight slots per item
     static constexpr int ITEM_SLOTS = HT + (WRES ? 0 : WT);
     static constexpr int PPW = (ITEM_SLOTS + 64 * NW - 1) / (64 * NW);  // 1-KiB DMA pieces per wave per item
@@ -89,9 +87,9 @@ struct SParams {
     int img;  // w is the slot-order weight image (tconv16_pack_weights, BM = 128): 1 KB contiguous per DMA piece
 };
 
-template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM, bool PM>
+template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM>
 __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
-    using G = SCfg<CIN, H, W, TH, NB, WRES, BM, PM>;
+    using G = SCfg<CIN, H, W, TH, NB, WRES, BM>;
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -126,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
         const int s = (j * G::NW + vwave(v)) * 64 + lane;
         int kind = 0, off = 0, nb = 0, hy = 0;
         if (s < G::HT) {
-            const int qh = PM ? s & 1 : s / G::HS, hs = PM ? s >> 1 : s - (s / G::HS) * G::HS;
+            const int qh = s & 1, hs = s >> 1;
             nb = hs / (4 * G::PH);
             const int rem = hs - nb * (4 * G::PH);
             const int ph = rem / G::PH, rr = rem - (rem / G::PH) * G::PH;
@@ -203,29 +201,13 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
     for (int k = 0; k < n_items; k++) {
         const int buf = k & 1, slice = k % G::NCH;
         const bool first = slice == 0, last = slice == G::NCH - 1;
-        // item k's DMA has landed (younger: only the previous tile's stores); the barrier
-        // publishes all waves' pieces and retires every read of the other ring slot
-        if (k == 0 || !first)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::STORES) : "memory");
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        item_wait_barrier<G::STORES>(k, first);
         const int tile = blockIdx.x + (k / G::NCH) * gridDim.x;
         int n0, ho0, cb;
         tile_of(tile, n0, ho0, cb);
         const int cob = cb * BM + mg * 32 + 16 * h;  // this lane's 16 couts
         if (first) {
-            f32x16 b;
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const float4 b4 = *reinterpret_cast<const float4*>(p.bias + cob + 4 * j);
-                b[4 * j] = b4.x;
-                b[4 * j + 1] = b4.y;
-                b[4 * j + 2] = b4.z;
-                b[4 * j + 3] = b4.w;
-            }
+            const f32x16 b = load_f32x16(p.bias + cob);
 #pragma unroll
             for (int t = 0; t < G::NT; t++) acc[t] = b;
         }
@@ -239,7 +221,6 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
 #pragma unroll
         for (int t = 0; t < G::NT; t++) bva[t] = bv[t] + boff;
         const int ava = WRES ? av + slice * G::WT * 16 : av + boff;
-        bf16x8 fa[2], fb[2][G::NT];
         auto load = [&](int tap, bf16x8& a, bf16x8 (&b)[G::NT]) {
             const int dy = tap / 3, dx = tap % 3;
             const int toff = ((dy & 1) * 2 + (dx & 1)) * G::PH + (dy >> 1) * G::RS + (dx >> 1);
@@ -247,6 +228,7 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
 #pragma unroll
             for (int t = 0; t < G::NT; t++) b[t] = *reinterpret_cast<const bf16x8*>(lds + bva[t] + toff * G::PS * 16);
         };
+        bf16x8 fa[2], fb[2][G::NT];
         load(0, fa[0], fb[0]);
 #pragma unroll
         for (int tap = 0; tap < 9; tap++) {
@@ -277,49 +259,23 @@ __global__ __launch_bounds__(512, 1) void s2conv_kernel(SParams p) {
             for (int t = 0; t < G::NT; t++) {
                 const bool ok = n0 + enb[t] < p.N && cok;
                 uint16_t* yrow = ok ? yb + (pix0 + eoff[t]) * cs + cl : p.sink + lane * 16;
-                uint32_t o[8];
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    float v0 = acc[t][2 * e], v1 = acc[t][2 * e + 1];
-                    if (rl) {
-                        v0 = relu1(v0);
-                        v1 = relu1(v1);
-                    }
-                    o[e] = pack_bf16x2(v0, v1);
-                }
-                *reinterpret_cast<uint4*>(yrow) = uint4{o[0], o[1], o[2], o[3]};
-                *reinterpret_cast<uint4*>(yrow + 8) = uint4{o[4], o[5], o[6], o[7]};
+                store_row16(yrow, pack_row16(acc[t], rl != 0));
             }
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-uint16_t* g_s_sink = nullptr;
-
-template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM, bool PM>
-void launch_sp_pm(SParams p, hipStream_t s) {
-    using G = SCfg<CIN, H, W, TH, NB, WRES, BM, PM>;
-    auto kern = s2conv_kernel<CIN, H, W, TH, NB, WRES, BM, PM>;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
-    const int grid = std::min(p.n_tiles, cu_count());
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT_THREADS), G::LDS, s, p);
-}
-
-// the pixel-major halo (+0.7 % frames/s over plane-major, round 2)
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM>
-void launch_sp(SParams p, hipStream_t s) {
-    launch_sp_pm<CIN, H, W, TH, NB, WRES, BM, true>(p, s);
+void launch_sp(const SParams& p, hipStream_t s) {
+    using G = SCfg<CIN, H, W, TH, NB, WRES, BM>;
+    const int grid = std::min(p.n_tiles, cu_count());
+    launch_lds<s2conv_kernel<CIN, H, W, TH, NB, WRES, BM>, G::LDS>(grid, G::NT_THREADS, s, p);
 }
 
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM>
 void launch_s(const ConvLaunch& c, hipStream_t s) {
     using G = SCfg<CIN, H, W, TH, NB, WRES, BM>;
-    if (!g_s_sink) MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
     MVP_REQUIRE(!WRES || c.Cout == BM, "s2conv: resident weights need Cout == BM");
     MVP_REQUIRE(c.Cout % BM == 0, "s2conv: Cout %d not a multiple of %d", c.Cout, BM);
     MVP_REQUIRE(c.Cin == CIN && c.H == H && c.W == W, "s2conv: plane mismatch");
@@ -327,13 +283,9 @@ void launch_s(const ConvLaunch& c, hipStream_t s) {
     MVP_REQUIRE(tiles < (1L << 30), "s2conv: too many tiles");
     // streamed weights from the graph's weight image when it made one (BM = 128 layout)
     const bool img = !WRES && BM == 128 && c.w_img != nullptr;
-    SParams p{c.x, img ? c.w_img : c.w, c.bias, c.y, conv_zero_region(), g_s_sink, c.N, c.Cout, (int)tiles,
+    SParams p{c.x, img ? c.w_img : c.w, c.bias, c.y, conv_zero_region(), conv_sink_region(), c.N, c.Cout, (int)tiles,
               c.Cout / BM, c.relu, nullptr, nullptr, 0, 0, 0, 0, img ? 1 : 0};
     launch_sp<CIN, H, W, TH, NB, WRES, BM>(p, s);
-}
-
-void init_s() {
-    if (!g_s_sink) MVP_HIP(hipMalloc(&g_s_sink, 64 * 32));
 }
 
 }  // namespace
@@ -353,10 +305,9 @@ void launch_s2conv_multi(const S2Multi& m, hipStream_t s) {
         tot += m.cout[i];
     }
     MVP_REQUIRE(s2conv_multi_supported(m.H, m.W, m.Cin, tot), "s2conv_multi: unsupported plane");
-    init_s();
     using G = SCfg<32, 64, 48, 8, 1, true, 128>;
     const long tiles = (long)m.N * (G::HO / 8);
-    SParams p{m.x, m.w, m.bias, m.y[0], conv_zero_region(), g_s_sink, m.N, m.cout[0], (int)tiles, 1, m.relu[0],
+    SParams p{m.x, m.w, m.bias, m.y[0], conv_zero_region(), conv_sink_region(), m.N, m.cout[0], (int)tiles, 1, m.relu[0],
               m.n_out > 1 ? m.y[1] : nullptr, m.n_out > 2 ? m.y[2] : nullptr, m.n_out > 1 ? m.cout[1] : 0,
               m.n_out > 2 ? m.cout[2] : 0, m.n_out > 1 ? m.relu[1] : 0, m.n_out > 2 ? m.relu[2] : 0, 0};
     if (tiles == 0) return;

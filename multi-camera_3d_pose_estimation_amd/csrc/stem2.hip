@@ -34,7 +34,6 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;
 
 struct S2 {
     static constexpr int H = 256, W = 192, W1 = 96, H2 = 64, W2 = 48;
@@ -171,19 +170,7 @@ __global__ __launch_bounds__(512, 1) void stem2_tile_kernel(StemParams p) {
         e2 = lr * G::W2 + c;
     }
     const int av2 = G::W2OFF + (h * 64 + mg2 * 32 + r32) * 16;
-    auto bias16 = [&](int conv, int mg) {
-        f32x16 v;
-        const float4* b = reinterpret_cast<const float4*>(sbias + 64 * conv + mg * 32 + 16 * h);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float4 q = b[j];
-            v[4 * j] = q.x;
-            v[4 * j + 1] = q.y;
-            v[4 * j + 2] = q.z;
-            v[4 * j + 3] = q.w;
-        }
-        return v;
-    };
+    auto bias16 = [&](int conv, int mg) { return load_f32x16(sbias + 64 * conv + mg * 32 + 16 * h); };
 
     const int n_items = (p.n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1;
     issue(0);
@@ -266,12 +253,8 @@ __global__ __launch_bounds__(512, 1) void stem2_tile_kernel(StemParams p) {
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[cur], fb[cur], acc, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            uint32_t o[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) o[e] = pack_bf16x2(relu1(acc[2 * e]), relu1(acc[2 * e + 1]));
             uint16_t* yp = p.y + (((long)n * G::H2 + r0) * G::W2 + e2) * 64 + mg2 * 32 + 16 * h;
-            *reinterpret_cast<uint4*>(yp) = uint4{o[0], o[1], o[2], o[3]};
-            *reinterpret_cast<uint4*>(yp + 8) = uint4{o[4], o[5], o[6], o[7]};
+            store_row16(yp, pack_row16(acc, true));
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -407,19 +390,9 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
                         for (int dy = 0; dy < 3; dy++)
                             bvd[u][dy] = G::MOFF + ring(v0 + 2 * lr[u] + dy) + (h * G::RS + c[u]) * 16;
                     f32x16 acc[NU];
-                    {
-                        const float4* bb = reinterpret_cast<const float4*>(sbias + 64 + mg2 * 32 + 16 * h);
+                    acc[0] = load_f32x16(sbias + 64 + mg2 * 32 + 16 * h);
 #pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const float4 q = bb[j];
-                            acc[0][4 * j] = q.x;
-                            acc[0][4 * j + 1] = q.y;
-                            acc[0][4 * j + 2] = q.z;
-                            acc[0][4 * j + 3] = q.w;
-                        }
-#pragma unroll
-                        for (int u = 1; u < NU; u++) acc[u] = acc[0];
-                    }
+                    for (int u = 1; u < NU; u++) acc[u] = acc[0];
                     constexpr int kPF = NU == 2 ? 4 : 6;
                     bf16x8 fb[kPF + 1][NU];
                     auto load = [&](int st) {
@@ -442,13 +415,9 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
                     }
 #pragma unroll
                     for (int u = 0; u < NU; u++) {
-                        uint32_t o[8];
-#pragma unroll
-                        for (int e = 0; e < 8; e++) o[e] = pack_bf16x2(relu1(acc[u][2 * e]), relu1(acc[u][2 * e + 1]));
                         uint16_t* yp = p.y + (((long)(crop0 + cl) * G::H2 + 2 * s + lr[u]) * G::W2 + c[u]) * 64 +
                                        mg2 * 32 + 16 * h;
-                        *reinterpret_cast<uint4*>(yp) = uint4{o[0], o[1], o[2], o[3]};
-                        *reinterpret_cast<uint4*>(yp + 8) = uint4{o[4], o[5], o[6], o[7]};
+                        store_row16(yp, pack_row16(acc[u], true));
                     }
                     // the next strip's input has landed (the 2 NU stores are younger)
                     if constexpr (NU == 2)
@@ -511,18 +480,7 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
                 if (s == 0)  // conv1 row -1: conv2's zero padding
                     for (int i = (wave - 4) * 64 + lane; i < G::ROWB / 16; i += 256)
                         *reinterpret_cast<uint4*>(lds + G::MOFF + ring(v0) + i * 16) = uint4{0u, 0u, 0u, 0u};
-                f32x16 bias;
-                {
-                    const float4* bb = reinterpret_cast<const float4*>(sbias + mg1 * 32 + 16 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const float4 q = bb[j];
-                        bias[4 * j] = q.x;
-                        bias[4 * j + 1] = q.y;
-                        bias[4 * j + 2] = q.z;
-                        bias[4 * j + 3] = q.w;
-                    }
-                }
+                const f32x16 bias = load_f32x16(sbias + mg1 * 32 + 16 * h);
                 // a group's 24 input reads are issued one group ahead (the MFMAs of a 3-step
                 // group cover too little of the LDS latency on their own)
                 uint2 raw[2][3][3][2];
@@ -563,12 +521,10 @@ __global__ __launch_bounds__(512, 1) void stem2_kernel(StemParams p) {
 #pragma unroll
                     for (int i = 0; i < 3; i++) {
                         const int f = grp * 3 + i;
-                        uint32_t o[8];
-#pragma unroll
-                        for (int e = 0; e < 8; e++) o[e] = pack_bf16x2(relu1(acc[i][2 * e]), relu1(acc[i][2 * e + 1]));
+                        const Row16 o = pack_row16(acc[i], true);
                         uint8_t* d = lds + G::MOFF + ring(v0 + 1 + cro[f]) + mo[f];
-                        *reinterpret_cast<uint4*>(d) = uint4{o[0], o[1], o[2], o[3]};
-                        *reinterpret_cast<uint4*>(d + G::RS * 16) = uint4{o[4], o[5], o[6], o[7]};
+                        *reinterpret_cast<uint4*>(d) = o.lo;
+                        *reinterpret_cast<uint4*>(d + G::RS * 16) = o.hi;
                     }
                 }
             }
@@ -588,30 +544,19 @@ void launch_stem2(const uint16_t* x, const float* w1, const float* b1, const uin
                   uint16_t* y, int N, int H, int W, bool crop_ranges, hipStream_t s) {
     MVP_REQUIRE(H == S2::H && W == S2::W, "stem2: input %dx%d is not 256x192", H, W);
     if (N == 0) return;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)stem2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, S2S::LDS));
-        attr = true;
-    }
     if (!crop_ranges) {  // small / ragged batches: the tile kernel (bit-identical)
-        static bool attr_t = false;
-        if (!attr_t) {
-            MVP_HIP(hipFuncSetAttribute((const void*)stem2_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        S2::LDS));
-            attr_t = true;
-        }
         const long tiles = (long)N * (S2::H2 / S2::TR);
         MVP_REQUIRE(tiles < (1L << 30), "stem2: too many tiles");
         StemParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, (int)tiles};
         const int grid = (int)std::min<long>(tiles, cu_count());
-        hipLaunchKernelGGL(stem2_tile_kernel, dim3(grid), dim3(S2::NTH), S2::LDS, s, p);
+        launch_lds<stem2_tile_kernel, S2::LDS>(grid, S2::NTH, s, p);
         MVP_HIP(hipGetLastError());
         return;
     }
     MVP_REQUIRE(N < (1 << 24), "stem2: too many crops");
     StemParams p{x, w1, b1, w2, b2, y, conv_zero_region(), N, 0};
     const int grid = std::min(N, cu_count());
-    hipLaunchKernelGGL(stem2_kernel, dim3(grid), dim3(512), S2S::LDS, s, p);
+    launch_lds<stem2_kernel, S2S::LDS>(grid, 512, s, p);
     MVP_HIP(hipGetLastError());
 }
 

@@ -37,7 +37,6 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;  // 16-B slots of the shared zero region
 
 struct S32 {
     static constexpr int H = 64, W = 48, TH = 8, STRIPS = H / TH;
@@ -98,14 +97,6 @@ __device__ __forceinline__ void barrier() {
     asm volatile("" ::: "memory");
 }
 
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
-}
-
 // A fragments of one conv for lane (r32, h): cout row_cout(r32), k-step s = (tap s/2, half
 // s%2): input channels 16 (s%2) + 8h .. +7 (tblock32_kernel's weight slot order).
 __device__ __forceinline__ void load_weights(const uint16_t* __restrict__ w, int r32, int h, bf16x8 (&wa)[S32::KS]) {
@@ -117,17 +108,7 @@ __device__ __forceinline__ void load_weights(const uint16_t* __restrict__ w, int
 
 // The accumulators start at the lane's 16 biases (couts 16h .. 16h+15) from LDS.
 __device__ __forceinline__ f32x16 bias_acc(const uint8_t* lds, int conv, int h) {
-    const float4* b = reinterpret_cast<const float4*>(lds + S32::BOFF + (32 * conv + 16 * h) * 4);
-    f32x16 r;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const float4 q = b[j];
-        r[4 * j] = q.x;
-        r[4 * j + 1] = q.y;
-        r[4 * j + 2] = q.z;
-        r[4 * j + 3] = q.w;
-    }
-    return r;
+    return load_f32x16(reinterpret_cast<const float*>(lds + S32::BOFF + (32 * conv + 16 * h) * 4));
 }
 
 // Strip g of this workgroup's crop range: crop-local index, strip in the crop.
@@ -354,25 +335,18 @@ __device__ __forceinline__ void conv2_role(const S32Params& p, uint8_t* lds, int
     auto epilogue = [&]() {
 #pragma unroll
         for (int t = 0; t < NF; t++) {
-            uint32_t o[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const uint4 rr = rv[t][e >> 2];
-                const uint32_t u = (e & 3) == 0 ? rr.x : (e & 3) == 1 ? rr.y : (e & 3) == 2 ? rr.z : rr.w;
-                o[e] = pack_bf16x2(relu1(acc[t][2 * e] + lo_bf16(u)), relu1(acc[t][2 * e + 1] + hi_bf16(u)));
-            }
+            const Row16 o = pack_row16(acc[t], true, rv[t][0], rv[t][1]);
             uint16_t* yp = p.y + (pix_prev + pr[t] * G::W + px[t]) * 32 + 16 * h;
 #ifdef TB32S_DIAG_NO_STORE  // stamps harness only: timing without the output stores (wrong results)
-            if ((o[0] ^ o[3] ^ o[5]) == 0x12345678u)
+            if ((o.lo.x ^ o.lo.w ^ o.hi.y) == 0x12345678u)
 #endif
             {
 #ifdef TB32S_NT_STORE  // A/B: non-temporal output stores
                 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(u32x4{o[0], o[1], o[2], o[3]}, reinterpret_cast<u32x4*>(yp));
-                __builtin_nontemporal_store(u32x4{o[4], o[5], o[6], o[7]}, reinterpret_cast<u32x4*>(yp + 8));
+                __builtin_nontemporal_store(u32x4{o.lo.x, o.lo.y, o.lo.z, o.lo.w}, reinterpret_cast<u32x4*>(yp));
+                __builtin_nontemporal_store(u32x4{o.hi.x, o.hi.y, o.hi.z, o.hi.w}, reinterpret_cast<u32x4*>(yp + 8));
 #else
-                *reinterpret_cast<uint4*>(yp) = uint4{o[0], o[1], o[2], o[3]};
-                *reinterpret_cast<uint4*>(yp + 8) = uint4{o[4], o[5], o[6], o[7]};
+                store_row16(yp, o);
 #endif
             }
         }
@@ -470,15 +444,10 @@ void launch_tblock32s(const uint16_t* x, const uint16_t* w1, const float* b1, co
     using G = S32;
     MVP_REQUIRE(H == G::H && W == G::W, "tblock32s: unsupported plane %dx%d", H, W);
     if (N == 0) return;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)tblock32s_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
     MVP_REQUIRE(N < (1 << 24), "tblock32s: too many crops");
     S32Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N};
     const int grid = std::min(N, cu_count());
-    hipLaunchKernelGGL(tblock32s_kernel, dim3(grid), dim3(512), G::LDS, s, p);
+    launch_lds<tblock32s_kernel, G::LDS>(grid, 512, s, p);
     MVP_HIP(hipGetLastError());
 }
 

@@ -48,7 +48,6 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;  // 16-B slots of the shared zero region
 
 struct B64 {
     static constexpr int H = 32, W = 24, TH = 8, RS = W + 2;
@@ -195,16 +194,6 @@ __device__ __forceinline__ void barrier() {
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-}
-
-// Compile-time loop: f(std::integral_constant<int, i>) for i in [B, E) — the step index is a
-// constant expression inside f (waitcnt immediates, buffer and fragment selection).
-template <int B, int E, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (B < E) {
-        f(std::integral_constant<int, B>{});
-        static_for<B + 1, E>(f);
-    }
 }
 
 // Both roles run their K loop as 72 steps: the first 36 accumulate the fragments of half A,
@@ -515,16 +504,8 @@ __device__ __forceinline__ void conv2_role(const TB64Params& p, uint8_t* lds, in
                     lds + mo + bv2[t0 + t] + ((4 * c + 2 * ks) * G::HSM + dy * RS + dx) * 16);
         };
         auto epilogue = [&](int t, int ci, const f32x16& a) {
-            uint32_t o[8];
-#pragma unroll
-            for (int e = 0; e < 8; e++) {
-                const uint4 rr = rv[t][ci][e >> 2];
-                const uint32_t u = (e & 3) == 0 ? rr.x : (e & 3) == 1 ? rr.y : (e & 3) == 2 ? rr.z : rr.w;
-                o[e] = pack_bf16x2(relu1(a[2 * e] + lo_bf16(u)), relu1(a[2 * e + 1] + hi_bf16(u)));
-            }
             uint16_t* yp = p.y + (pix0 + er * W + 4 * (f0 + t) + ex) * 64 + 32 * cg_of(ci) + 16 * h;
-            *reinterpret_cast<uint4*>(yp) = uint4{o[0], o[1], o[2], o[3]};
-            *reinterpret_cast<uint4*>(yp + 8) = uint4{o[4], o[5], o[6], o[7]};
+            store_row16(yp, pack_row16(a, true, rv[t][ci][0], rv[t][ci][1]));
         };
         static_for<0, PF>(load);
         static_for<0, 72>([&](auto Gs) {
@@ -608,21 +589,15 @@ void launch_tblock64(const uint16_t* x, const uint16_t* w1, const float* b1, con
     using G = B64;
     MVP_REQUIRE(H == G::H && W == G::W, "tblock64: unsupported plane %dx%d", H, W);
     if (N == 0) return;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)tblock64_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        MVP_HIP(hipFuncSetAttribute((const void*)tblock64_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
     const long tiles = (long)N * G::TILES_H;
     MVP_REQUIRE(tiles < (1L << 30), "tblock64: too many tiles");
     // contiguous crop ranges (conv1 reuses rows across a crop's tiles) from one crop per CU;
     // smaller batches: tiles strided over every CU, every tile computing all 10 rows
     TB64Params p{x, w1, b1, w2, b2, y, conv_zero_region(), N, (int)tiles};
     if (crop_ranges)
-        hipLaunchKernelGGL(tblock64_kernel<false>, dim3(std::min(N, cu_count())), dim3(256), G::LDS, s, p);
+        launch_lds<tblock64_kernel<false>, G::LDS>(std::min(N, cu_count()), 256, s, p);
     else
-        hipLaunchKernelGGL(tblock64_kernel<true>, dim3((int)std::min<long>(tiles, cu_count())), dim3(256), G::LDS, s, p);
+        launch_lds<tblock64_kernel<true>, G::LDS>((int)std::min<long>(tiles, cu_count()), 256, s, p);
     MVP_HIP(hipGetLastError());
 }
 

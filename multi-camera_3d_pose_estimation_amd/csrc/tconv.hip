@@ -44,9 +44,6 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;  // 16-B slots of the shared zero region
-
-
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM_ = 64, bool PM_ = false>
 struct TCfg {
     static constexpr int NW = 8, NT_THREADS = NW * 64;
@@ -191,18 +188,7 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
     // compiler wait for ALL outstanding VMEM (vmcnt(0): the next item's DMA, issued after
     // it) before the tile's first MFMA; from LDS, it waited for the previous tile's stores
     // (a conservative LDS-DMA alias wait before the read).
-    f32x16 bias_init;
-    {
-        const float* bp = p.bias + (blockIdx.x % p.ncb) * G::BM + mg * 32 + 16 * h;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const float4 b4 = *reinterpret_cast<const float4*>(bp + 4 * j);
-            bias_init[4 * j] = b4.x;
-            bias_init[4 * j + 1] = b4.y;
-            bias_init[4 * j + 2] = b4.z;
-            bias_init[4 * j + 3] = b4.w;
-        }
-    }
+    const f32x16 bias_init = load_f32x16(p.bias + (blockIdx.x % p.ncb) * G::BM + mg * 32 + 16 * h);
     if (WRES) {  // all weight chunks, once (column block 0: host guarantees ncb == 1)
 #pragma unroll
         for (int j = 0; j < G::WPPW; j++) {
@@ -217,15 +203,7 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
     for (int k = 0; k < n_items; k++) {
         const int buf = k & 1, chunk = k % G::NCH;
         const bool first = chunk == 0, last = chunk == G::NCH - 1;
-        // item k's DMA has landed (younger: only the previous tile's stores); the barrier
-        // publishes all waves' pieces and retires every read of the other ring slot
-        if (k == 0 || !first)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::STORES) : "memory");
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        item_wait_barrier<G::STORES>(k, first);
         const int tile = blockIdx.x + (k / G::NCH) * gridDim.x;
         int n0, ho0, cb;
         tile_of(tile, n0, ho0, cb);
@@ -261,10 +239,7 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
 #pragma unroll
         for (int t = 0; t < G::NT; t++) bva[t] = bv[t] + boff;
         const int ava = WRES ? av + chunk * G::WT * 16 : av + boff;
-        // fragments of step s+LD are read before step s's MFMAs (LD = LDS read look-ahead; 2
-        // measured level with 1: the loop is not LDS-latency bound)
-        constexpr int LD = 1, NBF = LD + 1;
-        bf16x8 fa[NBF], fb[NBF][G::NT];
+        // (a look-ahead of 2 steps measured level with 1: the loop is not LDS-latency bound)
         auto load = [&](int step, bf16x8& a, bf16x8 (&b)[G::NT]) {
             const int tap = step >> 1, ks = step & 1;
             const int dy = tap / 3, dx = tap % 3;
@@ -274,12 +249,12 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
                 b[t] = *reinterpret_cast<const bf16x8*>(lds + bva[t] +
                                                         (ks * 2 * G::QSTRIDE + (dy * G::RS + dx) * G::PSTRIDE) * 16);
         };
-#pragma unroll
-        for (int s0 = 0; s0 < LD; s0++) load(s0, fa[s0], fb[s0]);
+        bf16x8 fa[2], fb[2][G::NT];
+        load(0, fa[0], fb[0]);
 #pragma unroll
         for (int step = 0; step < 18; step++) {
-            const int cur = step % NBF;
-            if (step + LD < 18) load(step + LD, fa[(step + LD) % NBF], fb[(step + LD) % NBF]);
+            const int cur = step & 1;
+            if (step + 1 < 18) load(step + 1, fa[cur ^ 1], fb[cur ^ 1]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int t = 0; t < G::NT; t++)
@@ -293,51 +268,29 @@ __global__ __launch_bounds__(512, 1) void tconv_kernel(TParams p) {
             for (int t = 0; t < G::NT; t++) {
                 const bool ok = n0 + enb[t] < p.N;
                 uint16_t* yrow = ok ? p.y + (pix0 + eoff[t]) * p.Cout + cob : p.sink + lane * 16;
-                uint32_t o[8];
-#pragma unroll
-                for (int e = 0; e < 8; e++) {
-                    float v0 = acc[t][2 * e], v1 = acc[t][2 * e + 1];
-                    if (RES) {
-                        const uint4 rr = rv[t][e >> 2];
-                        const uint32_t u = (e & 3) == 0 ? rr.x : (e & 3) == 1 ? rr.y : (e & 3) == 2 ? rr.z : rr.w;
-                        v0 += lo_bf16(u);
-                        v1 += hi_bf16(u);
-                    }
-                    o[e] = pack_bf16x2(relu1(v0), relu1(v1));
-                }
-                *reinterpret_cast<uint4*>(yrow) = uint4{o[0], o[1], o[2], o[3]};
-                *reinterpret_cast<uint4*>(yrow + 8) = uint4{o[4], o[5], o[6], o[7]};
+                store_row16(yrow, RES ? pack_row16(acc[t], true, rv[t][0], rv[t][1]) : pack_row16(acc[t], true));
             }
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-uint16_t* g_t_sink = nullptr;
-
 template <int CIN, int H, int W, int TH, int NB, bool WRES, bool RES, int BM, bool PM>
 void launch_t_kernel(const TParams& p, hipStream_t s) {
     using G = TCfg<CIN, H, W, TH, NB, WRES, BM, PM>;
     static_assert(G::LDS <= 160 * 1024, "LDS budget");
-    auto kern = tconv_kernel<CIN, H, W, TH, NB, WRES, RES, BM, PM>;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
     const int grid = std::min(p.n_tiles, cu_count());
     MVP_REQUIRE(grid % p.ncb == 0, "tconv: grid %d not a multiple of the %d column blocks", grid, p.ncb);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT_THREADS), G::LDS, s, p);
+    launch_lds<tconv_kernel<CIN, H, W, TH, NB, WRES, RES, BM, PM>, G::LDS>(grid, G::NT_THREADS, s, p);
 }
 
 template <int CIN, int H, int W, int TH, int NB, bool WRES, int BM = 64>
 void launch_t(const ConvLaunch& c, hipStream_t s) {
-    if (!g_t_sink) MVP_HIP(hipMalloc(&g_t_sink, 64 * 32));
     MVP_REQUIRE(!WRES || c.Cout == BM, "tconv: resident weights need Cout == BM");
     MVP_REQUIRE(c.Cout % BM == 0, "tconv: Cout %d not a multiple of %d", c.Cout, BM);
     const long tiles = (long)((c.N + NB - 1) / NB) * (H / TH) * (c.Cout / BM);
     MVP_REQUIRE(tiles < (1L << 30), "tconv: too many tiles");
-    TParams p{c.x, c.w, c.bias, c.res, c.y, conv_zero_region(), g_t_sink, c.N, c.Cout, (int)tiles, c.Cout / BM};
+    TParams p{c.x, c.w, c.bias, c.res, c.y, conv_zero_region(), conv_sink_region(), c.N, c.Cout, (int)tiles, c.Cout / BM};
     // pixel-major halo wherever its 25 % larger ring slot still fits the LDS (+2.4-2.9 %
     // frames/s on the 64- and 256-ch planes, round 2), plane-major otherwise
     constexpr bool PM = TCfg<CIN, H, W, TH, NB, WRES, BM, true>::LDS <= 160 * 1024;

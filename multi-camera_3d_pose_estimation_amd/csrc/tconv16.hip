@@ -3,8 +3,8 @@
 //
 // tconv.hip's items are (384-pixel x 64-cout tile, 32 cin): for these planes the weights
 // do not fit the LDS, so every item streams a 37 KB weight slice plus a 40 KB halo, and
-// each wave reads 4 LDS fragments per 3 MFMAs.  Diagnostics on that kernel (MVPOSE_TCONV_DIAG,
-// profiles/r03t128_diag.txt) showed the MFMA work and the LDS-read / DMA work adding up
+// each wave reads 4 LDS fragments per 3 MFMAs.  Diagnostic builds of that kernel
+// (profiles/r03t128_diag.txt) showed the MFMA work and the LDS-read / DMA work adding up
 // instead of overlapping (61.6 us per conv without DMA or stores; 40.3 us with a third of
 // the MFMAs).  Here an item is (384 pixels x 128 couts, 16 cin):
 //
@@ -35,8 +35,6 @@ namespace mvp {
 namespace {
 
 using namespace mfma_tile;
-
-constexpr int kZeroSlots16 = 4096;
 
 template <int CIN, int H, int W, int TH, int NB, int BM>
 struct T16Cfg {
@@ -151,7 +149,7 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
         }
         pk[v][j] = (kind << 29) | (nb << 24) | (hy << 19) | off;
     }
-    const uint16_t* zl = p.zero + ((wave * 64 + lane) & (kZeroSlots16 - 1)) * 8;
+    const uint16_t* zl = p.zero + ((wave * 64 + lane) & (kZeroSlots - 1)) * 8;
 
     // tile -> (spatial tile, cout block), XCD-major: tiles t and t + 8 (same XCD under the
     // round-robin dispatch) are the two cout blocks of one spatial tile
@@ -211,13 +209,7 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
     for (int k = 0; k < n_items; k++) {
         const int buf = k & 1, chunk = k % G::NCH;
         const bool first = chunk == 0, last = chunk == G::NCH - 1;
-        if (k == 0 || !first)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::STORES) : "memory");
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
+        item_wait_barrier<G::STORES>(k, first);
         const int tile = blockIdx.x + (k / G::NCH) * gridDim.x;
         int n0, ho0, cb;
         tile_of(tile, n0, ho0, cb);
@@ -253,8 +245,6 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
 #pragma unroll
         for (int t = 0; t < G::NT; t++) bva[t] = bv[t] + boff;
         const int ava = av + boff;
-        constexpr int NBF = 2;
-        bf16x8 fa[NBF][G::NA], fb[NBF][G::NT];
         auto load = [&](int tap, bf16x8 (&a)[G::NA], bf16x8 (&b)[G::NT]) {
             const int dy = tap / 3, dx = tap % 3;
 #pragma unroll
@@ -264,6 +254,7 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
             for (int t = 0; t < G::NT; t++)
                 b[t] = *reinterpret_cast<const bf16x8*>(lds + bva[t] + (dy * G::RS + dx) * 3 * 16);
         };
+        bf16x8 fa[2][G::NA], fb[2][G::NT];
         load(0, fa[0], fb[0]);
 #pragma unroll
         for (int tap = 0; tap < 9; tap++) {
@@ -293,44 +284,23 @@ __global__ __launch_bounds__(512, 1) void tconv16_kernel(T16Params p) {
                 for (int t = 0; t < G::NT; t++) {
                     const bool ok = n0 + eoff[t] / (H * W) < p.N;
                     uint16_t* yrow = ok ? p.y + (pix0 + eoff[t]) * p.Cout + cob + a * 32 : p.sink + lane * 16;
-                    uint32_t o[8];
-#pragma unroll
-                    for (int e = 0; e < 8; e++) {
-                        float v0 = acc[a][t][2 * e], v1 = acc[a][t][2 * e + 1];
-                        if (RES) {
-                            const uint4 rr = rv[a][t][e >> 2];
-                            const uint32_t u = (e & 3) == 0 ? rr.x : (e & 3) == 1 ? rr.y : (e & 3) == 2 ? rr.z : rr.w;
-                            v0 += lo_bf16(u);
-                            v1 += hi_bf16(u);
-                        }
-                        o[e] = pack_bf16x2(relu1(v0), relu1(v1));
-                    }
-                    *reinterpret_cast<uint4*>(yrow) = uint4{o[0], o[1], o[2], o[3]};
-                    *reinterpret_cast<uint4*>(yrow + 8) = uint4{o[4], o[5], o[6], o[7]};
+                    store_row16(yrow, RES ? pack_row16(acc[a][t], true, rv[a][t][0], rv[a][t][1])
+                                          : pack_row16(acc[a][t], true));
                 }
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-uint16_t* g_t16_sink = nullptr;
-
 template <int CIN, int H, int W, int TH, int NB, int BM, bool RES>
 void launch_k16(const T16Params& p, int grid, hipStream_t s) {
     using G = T16Cfg<CIN, H, W, TH, NB, BM>;
-    auto kern = tconv16_kernel<CIN, H, W, TH, NB, BM, RES>;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        attr = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(G::NT_THREADS), G::LDS, s, p);
+    launch_lds<tconv16_kernel<CIN, H, W, TH, NB, BM, RES>, G::LDS>(grid, G::NT_THREADS, s, p);
 }
 
 template <int CIN, int H, int W, int TH, int NB, int BM>
 void launch_t16(const ConvLaunch& c, hipStream_t s) {
     static_assert(HMap<H, W, TH, NB>().balanced(), "halo residues must be balanced for the lane map");
-    if (!g_t16_sink) MVP_HIP(hipMalloc(&g_t16_sink, 64 * 32));
     MVP_REQUIRE(c.Cout % BM == 0, "tconv16: Cout %d not a multiple of %d", c.Cout, BM);
     const int ncb = c.Cout / BM;
     const long n_sp = (long)((c.N + NB - 1) / NB) * (H / TH);
@@ -340,7 +310,7 @@ void launch_t16(const ConvLaunch& c, hipStream_t s) {
     int grid = (int)std::min<long>(tiles, cu_count());
     if (grid < tiles) grid -= grid % (8 * ncb);  // fixed cout block per workgroup
     MVP_REQUIRE(grid > 0, "tconv16: %d CUs", cu_count());
-    T16Params p{c.x, c.w_img, c.bias, c.res, c.y, conv_zero_region(), g_t16_sink, c.N, c.Cout, (int)tiles, ncb};
+    T16Params p{c.x, c.w_img, c.bias, c.res, c.y, conv_zero_region(), conv_sink_region(), c.N, c.Cout, (int)tiles, ncb};
     if (c.res)
         launch_k16<CIN, H, W, TH, NB, BM, true>(p, grid, s);
     else

@@ -28,22 +28,18 @@ namespace {
 
 using namespace mfma_tile;
 
-constexpr int kZeroSlots = 4096;
-
-template <bool PM_>
 struct T1C {
     static constexpr int H = 64, W = 48, C = 256, TH = 16;
     static constexpr int NW = 8, NTH = NW * 64;
     static constexpr int NCH = C / 16;                     // 16-channel items per tile
     static constexpr int RS = W + 1, HR = TH + 2;          // halo row pitch (pixels), rows
     static constexpr int HS = 1 + HR * RS;                 // halo pixels (incl. the leading zero)
-    // PM (pixel-major halo): a pixel's two 16-B planes are slots 3p, 3p+1 (3p+2 a never-read
-    // pad): a DMA instruction reads ~21 pixels x 32 contiguous bytes instead of 64 pixels x
-    // 16 B (a third of the cache lines); the 48-B pixel pitch keeps 16 consecutive pixels'
-    // fragment reads on distinct banks.  Plane-major otherwise.
-    static constexpr bool PM = PM_;
-    static constexpr int QS = PM ? 1 : HS, PS = PM ? 3 : 1;  // slots between planes / pixels
-    static constexpr int WA = (PM ? 3 : 2) * HS;           // t0 weight slots [9][2][32]
+    // Pixel-major halo: a pixel's two 16-B planes are slots 3p, 3p+1 (3p+2 a never-read pad):
+    // a DMA instruction reads ~21 pixels x 32 contiguous bytes instead of 64 pixels x 16 B (a
+    // third of the cache lines); the 48-B pixel pitch keeps 16 consecutive pixels' fragment
+    // reads on distinct banks (+0.4 % frames/s over plane-major, round 2).
+    static constexpr int QS = 1, PS = 3;                   // slots between planes / pixels
+    static constexpr int WA = 3 * HS;                      // t0 weight slots [9][2][32]
     static constexpr int WB = WA + 9 * 2 * 32;             // t1 weight slots [9][2][64]
     static constexpr int ITEM = WB + 9 * 2 * 64;           // slots per item
     static constexpr int PPW = (ITEM + 64 * NW - 1) / (64 * NW);  // 1-KiB DMA pieces per wave per item
@@ -66,8 +62,6 @@ struct T1C {
 
 struct TrParams {
     const uint16_t* x;
-    const uint16_t* wb;  // weight blob: w0 [32][3][3][256] at element w0_off, w1 [64][3][3][256] at w1_off
-    int w0_off, w1_off;  // (one base pointer: per-piece source offsets stay 32-bit)
     const float* b0;
     const float* b1;
     uint16_t* y0;        // [N][64][48][32]
@@ -75,7 +69,7 @@ struct TrParams {
     const uint16_t* zero;
     int N, n_tiles;
     // the weight slots of every 16-channel chunk in LDS order (trans1_pack_weights): 1 KB
-    // contiguous per weight DMA instruction instead of 64 scattered rows; nullptr: gather from wb
+    // contiguous per weight DMA instruction instead of 64 scattered rows
     const uint16_t* wimg;
     // x in chunk-planar layout [N][16][64][48][16] (the fused Bottleneck's planar output): a
     // 16-channel item's halo is then one contiguous run per row, and no item shares a cache line
@@ -83,9 +77,8 @@ struct TrParams {
     int planar;
 };
 
-template <bool PM>
 __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
-    using G = T1C<PM>;
+    using G = T1C;
     extern __shared__ __attribute__((aligned(1024))) uint8_t lds[];
     const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, r32 = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
 
     // ---- per-lane DMA geometry of this wave's item pieces (fixed for the launch)
     // kind 1 halo: po = element offset from the tile's (crop, row -1, col 0) + chunk, hy = halo row;
-    // kind 2: weight element offset in the blob (t0 or t1 slice; + chunk * 16 at issue time)
+    // kind 2: weight element offset in the chunk's slice of the weight image
     // the t1 waves (4-7, half the MFMAs of a t0 wave) issue the item pieces of virtual waves
     // vw = wave & 3 and (wave & 3) + 4, the t0 waves none: after the item barrier the t0 wave of
     // each SIMD starts its MFMAs at once (tconv16.hip; 836 -> 811 us, profiles/r04_dma_split_ab.txt)
@@ -109,7 +102,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
         const int s = (j * G::NW + (wave & 3) + 4 * v) * 64 + lane;
         int kind = 0, off = 0, hy = 0;
         if (s < G::WA) {
-            const int q = PM ? s % 3 : s / G::HS, hs = PM ? s / 3 : s - q * G::HS;
+            const int q = s % 3, hs = s / 3;
             if (hs > 0 && q < 2) {
                 const int t = hs - 1, yy = t / G::RS, xx = t - yy * G::RS;
                 if (xx < G::W) {
@@ -118,17 +111,9 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
                     off = (yy * G::W + xx) * (p.planar ? 16 : G::C) + q * 8;
                 }
             }
-        } else if (s < G::ITEM && p.wimg) {
+        } else if (s < G::ITEM) {
             kind = 2;
             off = (s - G::WA) * 8;
-        } else if (s < G::WB) {
-            const int ws = s - G::WA, row = ws & 31, tq = ws >> 5;  // tq = tap * 2 + q
-            kind = 2;
-            off = p.w0_off + (row_cout(row) * 9 + (tq >> 1)) * G::C + (tq & 1) * 8;
-        } else if (s < G::ITEM) {
-            const int ws = s - G::WB, row = ws & 63, tq = ws >> 6;
-            kind = 2;
-            off = p.w1_off + (((row & ~31) | row_cout(row & 31)) * 9 + (tq >> 1)) * G::C + (tq & 1) * 8;
         }
         pk[v][j] = (kind << 8) | hy;
         po[v][j] = off;
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
         const uint16_t* xb = p.planar ? p.x + (((long)n * G::NCH + chunk) * G::H + r0 - 1) * G::W * 16
                                       : p.x + ((long)n * G::H + r0 - 1) * G::W * G::C + chunk * 16;
         uint8_t* dst = lds + buf * G::BUF;
-        const uint16_t* wbase = p.wimg ? p.wimg + chunk * (G::ITEM - G::WA) * 8 : p.wb + chunk * 16;
+        const uint16_t* wbase = p.wimg + chunk * (G::ITEM - G::WA) * 8;
         if (!dma_wave) return;
 #pragma unroll
         for (int v = 0; v < 2; v++)
@@ -205,16 +190,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
             const int tile = blockIdx.x + (k / G::NCH) * gridDim.x;
             const int n = tile / tiles_h, r0 = (tile - n * tiles_h) * G::TH;
             if (first) {
-                f32x16 b;
-                const float4* bp = reinterpret_cast<const float4*>(sbias + (S2C ? 32 + mg1 * 32 : 0) + 16 * h);
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float4 q = bp[j];
-                    b[4 * j] = q.x;
-                    b[4 * j + 1] = q.y;
-                    b[4 * j + 2] = q.z;
-                    b[4 * j + 3] = q.w;
-                }
+                const f32x16 b = load_f32x16(sbias + (S2C ? 32 + mg1 * 32 : 0) + 16 * h);
 #pragma unroll
                 for (int i = 0; i < NF; i++) acc[i] = b;
             }
@@ -222,7 +198,6 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
             asm volatile("" ::: "memory");
             const int boff = buf * G::BUF;
             // 9 taps x 1 k-step (16 channels); fragments of tap t+1 read before tap t's MFMAs
-            bf16x8 fa[2], fb[2][NF];
             auto load = [&](int tap, bf16x8& a, bf16x8 (&b)[NF]) {
                 const int dy = tap / 3, dx = tap % 3;
                 a = *reinterpret_cast<const bf16x8*>(lds + boff + av + tap * AST);
@@ -230,6 +205,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
                 for (int t = 0; t < NF; t++)
                     b[t] = *reinterpret_cast<const bf16x8*>(lds + boff + bv[t] + (dy * G::RS + dx) * G::PS * 16);
             };
+            bf16x8 fa[2], fb[2][NF];
             load(0, fa[0], fb[0]);
 #pragma unroll
             for (int tap = 0; tap < 9; tap++) {
@@ -245,14 +221,8 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
                 uint16_t* base = S2C ? p.y1 + ((long)n * (G::H / 2) + r0 / 2) * G::W1 * 64 + mg1 * 32 + 16 * h
                                      : p.y0 + ((long)n * G::H + r0) * G::W * 32 + 16 * h;
 #pragma unroll
-                for (int t = 0; t < NF; t++) {
-                    uint32_t o[8];
-#pragma unroll
-                    for (int e = 0; e < 8; e++) o[e] = pack_bf16x2(relu1(acc[t][2 * e]), relu1(acc[t][2 * e + 1]));
-                    uint16_t* yp = base + (long)eo[t] * (S2C ? 64 : 32);
-                    *reinterpret_cast<uint4*>(yp) = uint4{o[0], o[1], o[2], o[3]};
-                    *reinterpret_cast<uint4*>(yp + 8) = uint4{o[4], o[5], o[6], o[7]};
-                }
+                for (int t = 0; t < NF; t++)
+                    store_row16(base + (long)eo[t] * (S2C ? 64 : 32), pack_row16(acc[t], true));
             }
         }
     };
@@ -266,7 +236,7 @@ __global__ __launch_bounds__(512, 1) void trans1_kernel(TrParams p) {
 }  // namespace
 
 bool trans1_supported(int H, int W, int C, int cout0, int cout1) {
-    return H == T1C<true>::H && W == T1C<true>::W && C == T1C<true>::C && cout0 == 32 && cout1 == 64;
+    return H == T1C::H && W == T1C::W && C == T1C::C && cout0 == 32 && cout1 == 64;
 }
 
 // Weight image: per 16-channel chunk, t0's [tap][q][32 permuted couts] then t1's [tap][q][64]
@@ -289,29 +259,22 @@ __global__ __launch_bounds__(256) void trans1_pack_kernel(const uint16_t* __rest
 }
 
 void trans1_pack_weights(const uint16_t* wb, int64_t w0_off, int64_t w1_off, uint16_t* img, hipStream_t s) {
-    static_assert(T1C<true>::ITEM - T1C<true>::WA == 9 * 2 * 96, "image item");
+    static_assert(T1C::ITEM - T1C::WA == 9 * 2 * 96, "image item");
+    MVP_REQUIRE(w0_off >= 0 && w1_off >= 0 && w0_off + 32 * 9 * 256 < (1LL << 31) && w1_off + 64 * 9 * 256 < (1LL << 31),
+                "trans1: weight offsets exceed 32 bits");
     hipLaunchKernelGGL(trans1_pack_kernel, dim3(108), dim3(256), 0, s, wb, (int)w0_off, (int)w1_off, img);
     MVP_HIP(hipGetLastError());
 }
 
-void launch_trans1(const uint16_t* x, const uint16_t* wb, int64_t w0_off, const float* b0, int64_t w1_off,
-                   const float* b1, uint16_t* y0, uint16_t* y1, int N, hipStream_t s, const uint16_t* wimg,
-                   bool planar) {
-    MVP_REQUIRE(w0_off >= 0 && w1_off >= 0 && w0_off + 32 * 9 * 256 < (1LL << 31) && w1_off + 64 * 9 * 256 < (1LL << 31),
-                "trans1: weight offsets exceed 32 bits");
+void launch_trans1(const uint16_t* x, const uint16_t* wimg, const float* b0, const float* b1, uint16_t* y0,
+                   uint16_t* y1, int N, bool planar, hipStream_t s) {
+    MVP_REQUIRE(wimg, "trans1: no weight image");
     if (N == 0) return;
-    static bool attr = false;
-    if (!attr) {
-        MVP_HIP(hipFuncSetAttribute((const void*)trans1_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    T1C<true>::LDS));
-        attr = true;
-    }
-    const long tiles = (long)N * (T1C<true>::H / T1C<true>::TH);
-    MVP_REQUIRE(tiles * T1C<true>::NCH < (1L << 30), "trans1: too many tiles");
-    TrParams p{x, wb, (int)w0_off, (int)w1_off, b0, b1, y0, y1, conv_zero_region(), N, (int)tiles, wimg, planar ? 1 : 0};
+    const long tiles = (long)N * (T1C::H / T1C::TH);
+    MVP_REQUIRE(tiles * T1C::NCH < (1L << 30), "trans1: too many tiles");
+    TrParams p{x, b0, b1, y0, y1, conv_zero_region(), N, (int)tiles, wimg, planar ? 1 : 0};
     const int grid = (int)std::min<long>(tiles, cu_count());
-    // pixel-major halo (+0.4 % frames/s over plane-major, round 2)
-    hipLaunchKernelGGL(trans1_kernel<true>, dim3(grid), dim3(T1C<true>::NTH), T1C<true>::LDS, s, p);
+    launch_lds<trans1_kernel, T1C::LDS>(grid, T1C::NTH, s, p);
     MVP_HIP(hipGetLastError());
 }
 

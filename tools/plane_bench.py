@@ -1,6 +1,5 @@
 """BasicBlock planes with the graph's default kernels at the bench batch (1024 crops):
-us per conv (HIP events on torch's stream).  Diagnostics through the kernels' env
-switches (e.g. MVPOSE_TCONV_DIAG).
+us per conv (HIP events on torch's stream).
     python tools/plane_bench.py [reps] [C,H,W ...]"""
 import os
 import sys
