@@ -9,17 +9,17 @@
 //              the f64 copy of the seed, and how many active points observe each view.
 //   linearise  workgroups of one wavefront (as many per CU as its LDS holds, at most one per SIMD),
 //              grid-stride over the points, one lane per point.  One LDS image serves in turn A
-//              beside B and then Y.  A
-//              lane walks its views twice in rolled loops (camera records through wave-uniform
-//              addresses).  Walk 1: V_p, g_p, the cost, g_c into lane-private LDS columns, and for
-//              every free view the images A = J_cᵀ·W̃ and B = J_cᵀ (rows 6·slot.., k = (component,
-//              lane)); then U += A·Bᵀ by v_mfma_f64_16x16x4_f64 over the upper 16x16 tiles.  The
-//              views share the k columns, so only the diagonal 6x6 blocks of the product are U_i;
-//              the rest is never read.  (A·Bᵀ and not a square root of W̃: a weight need not be
-//              positive.)  Walk 2, after the 3x3 Cholesky: Y_p's rows and, in padding row 6F, the
-//              row (L⁻¹·g_p)ᵀ, so that column 6F of Σ Y·Yᵀ is b's correction; Σ Y·Yᵀ by the same
-//              MFMA loop, A and B fragments being the same registers.  The accumulators live in
-//              registers across the whole grid-stride loop; a workgroup writes ONE partial record.
+//              beside B and then Y.  A lane walks its views twice in rolled loops (camera records
+//              through wave-uniform addresses).  Walk 1: V_p, g_p, the cost, g_c into lane-private
+//              LDS columns, and for every free view the images A = J_cᵀ·W̃ and B = J_cᵀ (rows
+//              6·slot.., k = (component, lane)); then U += A·Bᵀ by v_mfma_f64_16x16x4_f64 over the
+//              upper 16x16 tiles.  The views share the k columns, so only the diagonal 6x6 blocks of
+//              the product are U_i; the rest is never read.  (A·Bᵀ and not a square root of W̃: a
+//              weight need not be positive.)  Walk 2, after the 3x3 Cholesky: Y_p's rows and, in
+//              padding row 6F, the row (L⁻¹·g_p)ᵀ, so that column 6F of Σ Y·Yᵀ is b's correction;
+//              Σ Y·Yᵀ by the same MFMA loop, A and B fragments being the same registers.  The
+//              accumulators live in registers across the whole grid-stride loop; a workgroup writes
+//              ONE partial record.
 //   solve      one workgroup: partial records summed in index order (no atomics: the same inputs
 //              give the same bits), damping and prior, Cholesky of S, δc, the trial cameras.
 //   points     one lane per point: δX_p from δc with W_pi recomputed, the trial point, and the
@@ -67,18 +67,9 @@ struct BaState {
 };
 
 struct BaViews {
-    unsigned cols;       // the listed cameras as nibbles
+    ViewList vl;         // the listed cameras
     unsigned free_mask;  // bit j: view j is optimised
-    int nv, F;
-};
-
-struct BaObsArgs {
-    const float* kpts;
-    const uint8_t* mask;
-    const double* gauss;
-    int64_t n;
-    int V, weights, J;
-    float min_conf, cov_floor;
+    int F;
 };
 
 struct BaPlan {
@@ -116,58 +107,8 @@ inline BaPlan ba_plan(const char* fn, int64_t n, int nv, unsigned free_mask) {
     return pl;
 }
 
-// ------------------------------------------------------------------------------- one view's terms
-struct BaView {
-    double r0, r1, w00, w01, w11, rho;   // residual, W̃ = ω·W, ρ(s)
-    double jx0[3], jx1[3];               // J_X
-    double jc0[6], jc1[6];               // J_c
-    bool front;
-};
-
-// Residual, Huber weight and cost of a view; JAC: also J_X and J_c = A·[−[P−T]×, I].
-template <bool JAC>
-__device__ __forceinline__ void ba_view(const RefineCam& c, const double (&X)[3], double zx, double zy, double wxx,
-                                        double wxy, double wyy, double hub, BaView& o) {
-#pragma clang fp contract(fast)
-    const RefineFwd w = refine_forward(c, X);
-    o.front = w.Pz > 0;
-    o.r0 = w.u - zx;
-    o.r1 = w.v - zy;
-    const double s2 = o.r0 * (wxx * o.r0 + wxy * o.r1) + o.r1 * (wxy * o.r0 + wyy * o.r1);
-    const double s = sqrt(s2);
-    const bool quad = !(hub > 0) || !(s > hub);
-    const double om = quad ? 1.0 : hub / s;
-    o.rho = quad ? 0.5 * s2 : hub * (s - 0.5 * hub);
-    o.w00 = om * wxx, o.w01 = om * wxy, o.w11 = om * wyy;
-    if (JAC) {
-        // d pixel / dP = A·[[iz, 0, −x·iz], [0, iz, −y·iz]]
-        const double p00 = w.a00 * w.iz, p01 = w.a01 * w.iz, p02 = -(w.a00 * w.x + w.a01 * w.y) * w.iz;
-        const double p10 = w.a10 * w.iz, p11 = w.a11 * w.iz, p12 = -(w.a10 * w.x + w.a11 * w.y) * w.iz;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            o.jx0[k] = p00 * c.R[k] + p01 * c.R[3 + k] + p02 * c.R[6 + k];
-            o.jx1[k] = p10 * c.R[k] + p11 * c.R[3 + k] + p12 * c.R[6 + k];
-        }
-        const double qx = w.Px - c.T[0], qy = w.Py - c.T[1], qz = w.Pz - c.T[2];
-        o.jc0[0] = p02 * qy - p01 * qz, o.jc0[1] = p00 * qz - p02 * qx, o.jc0[2] = p01 * qx - p00 * qy;
-        o.jc1[0] = p12 * qy - p11 * qz, o.jc1[1] = p10 * qz - p12 * qx, o.jc1[2] = p11 * qx - p10 * qy;
-        o.jc0[3] = p00, o.jc0[4] = p01, o.jc0[5] = p02;
-        o.jc1[3] = p10, o.jc1[4] = p11, o.jc1[5] = p12;
-    }
-}
-
-// The point's observation of view j (column col), by the rule of refine_common.h.
-__device__ __forceinline__ bool ba_observe(const BaObsArgs& a, int64_t p, int col, bool allowed, double& zx, double& zy,
-                                           double& wxx, double& wxy, double& wyy) {
-    const bool gs = a.weights == MVP_REFINE_W_GAUSS;
-    const int64_t gt = gs ? p / a.J : 0;
-    const int gj = gs ? (int)(p % a.J) : 0;
-    return refine_observation(a.kpts + p * 3 * a.V, a.V, col, allowed, a.weights, a.gauss, gt, gj, a.J, a.min_conf,
-                              a.cov_floor, zx, zy, wxx, wxy, wyy);
-}
-
 // ------------------------------------------------------------------------------- prepare
-__global__ __launch_bounds__(kBlock) void ba_prepare_kernel(BaObsArgs a, const double* __restrict__ cams, BaViews vw,
+__global__ __launch_bounds__(kBlock) void ba_prepare_kernel(ReprojObs a, const double* __restrict__ cams, BaViews vw,
                                                             const float* __restrict__ xyz0,
                                                             uint8_t* __restrict__ used_out, double* __restrict__ x0,
                                                             int* __restrict__ view_cnt) {
@@ -175,16 +116,16 @@ __global__ __launch_bounds__(kBlock) void ba_prepare_kernel(BaObsArgs a, const d
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const bool valid = p < a.n;
     const int64_t pc = valid ? p : 0;
-    const unsigned allowed = a.mask ? (unsigned)a.mask[pc] : 0xFFu;
+    const unsigned allowed = reproj_allowed(a, pc);
     const float s0 = xyz0[3 * pc + 0], s1 = xyz0[3 * pc + 1], s2 = xyz0[3 * pc + 2];
     const double X[3] = {(double)s0, (double)s1, (double)s2};
     unsigned used = 0;
     bool front = true;
 #pragma unroll 1
-    for (int j = 0; j < vw.nv; j++) {
-        const int col = (vw.cols >> (4 * j)) & 15u;
+    for (int j = 0; j < vw.vl.nv; j++) {
+        const int col = vw.vl.col(j);
         double zx, zy, wxx, wxy, wyy;
-        const bool ok = ba_observe(a, pc, col, (allowed >> j) & 1u, zx, zy, wxx, wxy, wyy);
+        const bool ok = reproj_observe(a, pc, col, (allowed >> j) & 1u, zx, zy, wxx, wxy, wyy);
         const RefineCam c = refine_cam(cams + col * MVP_CAM_DOUBLES);
         const double Pz = c.R[6] * X[0] + c.R[7] * X[1] + c.R[8] * X[2] + c.T[2];
         used |= (ok ? 1u : 0u) << j;
@@ -202,7 +143,7 @@ __global__ __launch_bounds__(kBlock) void ba_prepare_kernel(BaObsArgs a, const d
     }
     if (view_cnt) {
 #pragma unroll 1
-        for (int j = 0; j < vw.nv; j++) {
+        for (int j = 0; j < vw.vl.nv; j++) {
             const unsigned long long b = __ballot((used >> j) & 1u);
             if ((threadIdx.x & 63) == 0 && b) atomicAdd(view_cnt + j, (int)__builtin_popcountll(b));
         }
@@ -211,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void ba_prepare_kernel(BaObsArgs a, const d
 
 // ------------------------------------------------------------------------------- linearise
 struct BaLinArgs {
-    BaObsArgs obs;
+    ReprojObs obs;       // hub: the Huber delta
     BaViews vw;
     const BaState* st;        // null: mvp_bundle_adjust_system (cams, xyz32 and lambda below)
     const double* cams;
@@ -219,7 +160,7 @@ struct BaLinArgs {
     const double* x64;        // [2][n][3] with st
     const uint8_t* used;
     double* part;             // [gridDim][rec]
-    double lambda, hub;
+    double lambda;
     int final_pass;           // with st: run although done, with lambda = 0
 };
 
@@ -287,39 +228,27 @@ __global__ __launch_bounds__(kBaWave) void ba_linearise_kernel(BaLinArgs g) {
         // walk 1: V_p, g_p, cost, g_c and the A / B images
         double Vp[6] = {0, 0, 0, 0, 0, 0}, gp[3] = {0, 0, 0};
 #pragma unroll 1
-        for (int j = 0; j < g.vw.nv; j++) {
-            const int col = (g.vw.cols >> (4 * j)) & 15u;
+        for (int j = 0; j < g.vw.vl.nv; j++) {
+            const int col = g.vw.vl.col(j);
             const bool u = (used >> j) & 1u;
             double zx, zy, wxx, wxy, wyy;
-            ba_observe(g.obs, pc, col, u, zx, zy, wxx, wxy, wyy);
+            reproj_observe(g.obs, pc, col, u, zx, zy, wxx, wxy, wyy);
             const RefineCam c = refine_cam(cam_base + col * MVP_CAM_DOUBLES);
-            BaView o;
-            ba_view<true>(c, X, zx, zy, wxx, wxy, wyy, g.hub, o);
-            const double wr0 = o.w00 * o.r0 + o.w01 * o.r1, wr1 = o.w01 * o.r0 + o.w11 * o.r1;
-            double wj0[3], wj1[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                wj0[k] = o.w00 * o.jx0[k] + o.w01 * o.jx1[k];
-                wj1[k] = o.w01 * o.jx0[k] + o.w11 * o.jx1[k];
-                gp[k] += u ? o.jx0[k] * wr0 + o.jx1[k] * wr1 : 0.0;
-            }
-            Vp[0] += u ? o.jx0[0] * wj0[0] + o.jx1[0] * wj1[0] : 0.0;
-            Vp[1] += u ? o.jx0[0] * wj0[1] + o.jx1[0] * wj1[1] : 0.0;
-            Vp[2] += u ? o.jx0[0] * wj0[2] + o.jx1[0] * wj1[2] : 0.0;
-            Vp[3] += u ? o.jx0[1] * wj0[1] + o.jx1[1] * wj1[1] : 0.0;
-            Vp[4] += u ? o.jx0[1] * wj0[2] + o.jx1[1] * wj1[2] : 0.0;
-            Vp[5] += u ? o.jx0[2] * wj0[2] + o.jx1[2] * wj1[2] : 0.0;
+            const ReprojView o = reproj_view(c, X, zx, zy, wxx, wxy, wyy, g.obs.hub);
+            double jx0[3], jx1[3], jc0[6], jc1[6];
+            reproj_jx_jc(c, o.w, jx0, jx1, jc0, jc1);
+            reproj_add_normal(jx0, jx1, o.w00, o.w01, o.w11, o.r0, o.r1, u, gp, Vp);
             cost += u ? o.rho : 0.0;
             n_used += u ? 1 : 0;
             if ((g.vw.free_mask >> j) & 1u) {   // wave-uniform
                 const int row0 = 6 * __builtin_popcount(g.vw.free_mask & ((1u << j) - 1u));
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
-                    const double a0 = o.jc0[k] * o.w00 + o.jc1[k] * o.w01, a1 = o.jc0[k] * o.w01 + o.jc1[k] * o.w11;
+                    const double a0 = jc0[k] * o.w00 + jc1[k] * o.w01, a1 = jc0[k] * o.w01 + jc1[k] * o.w11;
                     s_y[(row0 + k) * kBaStride + lane] = u ? a0 : 0.0;
                     s_y[(row0 + k) * kBaStride + kBaWave + lane] = u ? a1 : 0.0;
-                    s_b[(row0 + k) * kBaStride + lane] = u ? o.jc0[k] : 0.0;
-                    s_b[(row0 + k) * kBaStride + kBaWave + lane] = u ? o.jc1[k] : 0.0;
+                    s_b[(row0 + k) * kBaStride + lane] = u ? jc0[k] : 0.0;
+                    s_b[(row0 + k) * kBaStride + kBaWave + lane] = u ? jc1[k] : 0.0;
                     s_gc[(row0 + k) * kBaWave + lane] += u ? a0 * o.r0 + a1 * o.r1 : 0.0;
                 }
             }
@@ -349,22 +278,23 @@ __global__ __launch_bounds__(kBaWave) void ba_linearise_kernel(BaLinArgs g) {
         }
         // walk 2: the free views' rows of Y_p = W_pi·L⁻ᵀ
 #pragma unroll 1
-        for (int j = 0; j < g.vw.nv; j++) {
+        for (int j = 0; j < g.vw.vl.nv; j++) {
             if (!((g.vw.free_mask >> j) & 1u)) continue;
             const int row0 = 6 * __builtin_popcount(g.vw.free_mask & ((1u << j) - 1u));
-            const int col = (g.vw.cols >> (4 * j)) & 15u;
+            const int col = g.vw.vl.col(j);
             const bool u = (used >> j) & 1u;
             double zx, zy, wxx, wxy, wyy;
-            ba_observe(g.obs, pc, col, u, zx, zy, wxx, wxy, wyy);
+            reproj_observe(g.obs, pc, col, u, zx, zy, wxx, wxy, wyy);
             const RefineCam c = refine_cam(cam_base + col * MVP_CAM_DOUBLES);
-            BaView o;
-            ba_view<true>(c, X, zx, zy, wxx, wxy, wyy, g.hub, o);
+            const ReprojView o = reproj_view(c, X, zx, zy, wxx, wxy, wyy, g.obs.hub);
+            double jx0[3], jx1[3], jc0[6], jc1[6];
+            reproj_jx_jc(c, o.w, jx0, jx1, jc0, jc1);
 #pragma unroll
             for (int k = 0; k < 6; k++) {
-                const double a0 = o.jc0[k] * o.w00 + o.jc1[k] * o.w01, a1 = o.jc0[k] * o.w01 + o.jc1[k] * o.w11;
-                const double w0 = a0 * o.jx0[0] + a1 * o.jx1[0];
-                const double w1 = a0 * o.jx0[1] + a1 * o.jx1[1];
-                const double w2 = a0 * o.jx0[2] + a1 * o.jx1[2];
+                const double a0 = jc0[k] * o.w00 + jc1[k] * o.w01, a1 = jc0[k] * o.w01 + jc1[k] * o.w11;
+                const double w0 = a0 * jx0[0] + a1 * jx1[0];
+                const double w1 = a0 * jx0[1] + a1 * jx1[1];
+                const double w2 = a0 * jx0[2] + a1 * jx1[2];
                 const double y0 = w0 * i0;
                 const double y1 = (w1 - L[1] * y0) * i3;
                 const double y2 = (w2 - L[2] * y0 - L[4] * y1) * i5;
@@ -502,9 +432,9 @@ __device__ __forceinline__ double ba_prior_cost(const double* cam, const double*
                                                 double inv_s2) {
 #pragma clang fp contract(fast)
     double s = 0.0;
-    for (int j = 0; j < vw.nv; j++) {
+    for (int j = 0; j < vw.vl.nv; j++) {
         if (!((vw.free_mask >> j) & 1u)) continue;
-        const int col = (vw.cols >> (4 * j)) & 15u;
+        const int col = vw.vl.col(j);
         for (int k = 0; k < 3; k++) {
             const double d = cam[col * MVP_CAM_DOUBLES + 23 + k] - cams0[col * MVP_CAM_DOUBLES + 23 + k];
             s += d * d;
@@ -521,7 +451,7 @@ __global__ void ba_init_kernel(BaState* st, const double* __restrict__ cams, int
     }
     if (threadIdx.x == 0) {
         bool starved = false;
-        for (int j = 0; j < vw.nv; j++) starved = starved || (((vw.free_mask >> j) & 1u) && st->view_cnt[j] < 3);
+        for (int j = 0; j < vw.vl.nv; j++) starved = starved || (((vw.free_mask >> j) & 1u) && st->view_cnt[j] < 3);
         st->lambda = 1e-3;
         st->f_cur = st->f_seed = 0.0;
         st->cur = 0;
@@ -545,9 +475,9 @@ __global__ __launch_bounds__(kBaSolveBlock) void ba_solve_kernel(BaState* st, co
     ba_sum_partials(part, n_part, ba_rec_doubles(nr), s_sum);
     if (threadIdx.x == 0) {
         int slot = 0;
-        for (int j = 0; j < vw.nv; j++) {
+        for (int j = 0; j < vw.vl.nv; j++) {
             if (!((vw.free_mask >> j) & 1u)) continue;
-            const int col = (vw.cols >> (4 * j)) & 15u;
+            const int col = vw.vl.col(j);
             for (int k = 0; k < 3; k++)
                 s_td[3 * slot + k] = camc[col * MVP_CAM_DOUBLES + 23 + k] - cams0[col * MVP_CAM_DOUBLES + 23 + k];
             slot++;
@@ -570,9 +500,9 @@ __global__ __launch_bounds__(kBaSolveBlock) void ba_solve_kernel(BaState* st, co
     for (int a = 0; a < kBaMaxRows; a++) st->dc[a] = (ok && a < n6) ? s_bv[a] : 0.0;
     // trial cameras: R <- exp([δw]×)·R, T <- T + δu
     int slot = 0;
-    for (int j = 0; j < vw.nv; j++) {
+    for (int j = 0; j < vw.vl.nv; j++) {
         if (!((vw.free_mask >> j) & 1u)) continue;
-        const int col = (vw.cols >> (4 * j)) & 15u;
+        const int col = vw.vl.col(j);
         const double* dc = st->dc + 6 * slot;
         const double* Rc = camc + col * MVP_CAM_DOUBLES + 14;
         double* Rt = camt + col * MVP_CAM_DOUBLES + 14;
@@ -598,13 +528,12 @@ __global__ __launch_bounds__(kBaSolveBlock) void ba_solve_kernel(BaState* st, co
 }
 
 struct BaPtArgs {
-    BaObsArgs obs;
+    ReprojObs obs;       // hub: the Huber delta
     BaViews vw;
     const BaState* st;
     double* x64;
     const uint8_t* used;
     double* tpart;   // [gridDim]
-    double hub;
 };
 
 __global__ __launch_bounds__(kBlock) void ba_points_kernel(BaPtArgs g) {
@@ -632,37 +561,25 @@ __global__ __launch_bounds__(kBlock) void ba_points_kernel(BaPtArgs g) {
         // rhs = g_p + Σ W_piᵀ·δc_i = Σ J_Xᵀ·W̃·(r + J_c·δc_i)
         double Vp[6] = {0, 0, 0, 0, 0, 0}, rhs[3] = {0, 0, 0};
 #pragma unroll 1
-        for (int j = 0; j < g.vw.nv; j++) {
-            const int col = (g.vw.cols >> (4 * j)) & 15u;
+        for (int j = 0; j < g.vw.vl.nv; j++) {
+            const int col = g.vw.vl.col(j);
             const bool u = (used >> j) & 1u;
             double zx, zy, wxx, wxy, wyy;
-            ba_observe(g.obs, p, col, u, zx, zy, wxx, wxy, wyy);
+            reproj_observe(g.obs, p, col, u, zx, zy, wxx, wxy, wyy);
             const RefineCam c = refine_cam(camc + col * MVP_CAM_DOUBLES);
-            BaView o;
-            ba_view<true>(c, X, zx, zy, wxx, wxy, wyy, g.hub, o);
+            const ReprojView o = reproj_view(c, X, zx, zy, wxx, wxy, wyy, g.obs.hub);
+            double jx0[3], jx1[3], jc0[6], jc1[6];
+            reproj_jx_jc(c, o.w, jx0, jx1, jc0, jc1);
             double t0 = o.r0, t1 = o.r1;
             if ((g.vw.free_mask >> j) & 1u) {
                 const double* dc = dcv + 6 * __builtin_popcount(g.vw.free_mask & ((1u << j) - 1u));
 #pragma unroll
                 for (int k = 0; k < 6; k++) {
-                    t0 += o.jc0[k] * dc[k];
-                    t1 += o.jc1[k] * dc[k];
+                    t0 += jc0[k] * dc[k];
+                    t1 += jc1[k] * dc[k];
                 }
             }
-            const double wt0 = o.w00 * t0 + o.w01 * t1, wt1 = o.w01 * t0 + o.w11 * t1;
-            double wj0[3], wj1[3];
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                wj0[k] = o.w00 * o.jx0[k] + o.w01 * o.jx1[k];
-                wj1[k] = o.w01 * o.jx0[k] + o.w11 * o.jx1[k];
-                rhs[k] -= u ? o.jx0[k] * wt0 + o.jx1[k] * wt1 : 0.0;
-            }
-            Vp[0] += u ? o.jx0[0] * wj0[0] + o.jx1[0] * wj1[0] : 0.0;
-            Vp[1] += u ? o.jx0[0] * wj0[1] + o.jx1[0] * wj1[1] : 0.0;
-            Vp[2] += u ? o.jx0[0] * wj0[2] + o.jx1[0] * wj1[2] : 0.0;
-            Vp[3] += u ? o.jx0[1] * wj0[1] + o.jx1[1] * wj1[1] : 0.0;
-            Vp[4] += u ? o.jx0[1] * wj0[2] + o.jx1[1] * wj1[2] : 0.0;
-            Vp[5] += u ? o.jx0[2] * wj0[2] + o.jx1[2] * wj1[2] : 0.0;
+            reproj_add_normal(jx0, jx1, o.w00, o.w01, o.w11, -t0, -t1, u, rhs, Vp);   // rhs −= J_Xᵀ·W̃·t, bit for bit
         }
         const double A[6] = {Vp[0] * damp, Vp[1], Vp[2], Vp[3] * damp, Vp[4], Vp[5] * damp};
         double L[6], dX[3];
@@ -674,14 +591,13 @@ __global__ __launch_bounds__(kBlock) void ba_points_kernel(BaPtArgs g) {
         double fp = 0.0;
         bool front = true;
 #pragma unroll 1
-        for (int j = 0; j < g.vw.nv; j++) {
-            const int col = (g.vw.cols >> (4 * j)) & 15u;
+        for (int j = 0; j < g.vw.vl.nv; j++) {
+            const int col = g.vw.vl.col(j);
             const bool u = (used >> j) & 1u;
             double zx, zy, wxx, wxy, wyy;
-            ba_observe(g.obs, p, col, u, zx, zy, wxx, wxy, wyy);
+            reproj_observe(g.obs, p, col, u, zx, zy, wxx, wxy, wyy);
             const RefineCam c = refine_cam(camt + col * MVP_CAM_DOUBLES);
-            BaView o;
-            ba_view<false>(c, Xn, zx, zy, wxx, wxy, wyy, g.hub, o);
+            const ReprojView o = reproj_view(c, Xn, zx, zy, wxx, wxy, wyy, g.obs.hub);
             fp += u ? o.rho : 0.0;
             front = front && (!u || o.front);
         }
@@ -774,8 +690,8 @@ __global__ __launch_bounds__(kBaSolveBlock) void ba_final_kernel(BaState* st, co
     // loops of mvp_camera_pack (no contraction)
     for (int e = threadIdx.x; e < n_cams * MVP_CAM_DOUBLES; e += blockDim.x) out_cams[e] = cams0[e];
     __syncthreads();
-    if ((int)threadIdx.x < vw.nv && ((vw.free_mask >> threadIdx.x) & 1u)) {
-        const int col = (vw.cols >> (4 * threadIdx.x)) & 15u;
+    if ((int)threadIdx.x < vw.vl.nv && ((vw.free_mask >> threadIdx.x) & 1u)) {
+        const int col = vw.vl.col(threadIdx.x);
         double* o = out_cams + col * MVP_CAM_DOUBLES;
         const double* c = camc + col * MVP_CAM_DOUBLES;
         for (int k = 14; k < 26; k++) o[k] = c[k];
@@ -811,8 +727,8 @@ __global__ __launch_bounds__(kBlock) void ba_output_kernel(const BaState* st, co
 struct BaCall {
     BaPlan pl;
     BaViews vw;
-    BaObsArgs obs;
-    double hub, inv_s2;
+    ReprojObs obs;
+    double inv_s2;
 };
 
 inline BaCall ba_parse(const char* fn, const float* kpts, int64_t n, int V, int n_cams, const int* cam_idx, int nv,
@@ -821,24 +737,11 @@ inline BaCall ba_parse(const char* fn, const float* kpts, int64_t n, int V, int 
     BaCall c{};
     const CamIdx ci = tri_parse_args(fn, n, V, n_cams, cam_idx, nv);
     c.pl = ba_plan(fn, n, nv, free_mask);
-    MVP_REQUIRE(weights >= MVP_REFINE_W_UNIT && weights <= MVP_REFINE_W_GAUSS, "%s: weights=%d (0..2)", fn, weights);
-    if (weights == MVP_REFINE_W_GAUSS) {
-        MVP_REQUIRE(gauss != nullptr, "%s: MVP_REFINE_W_GAUSS needs gauss_dev", fn);
-        MVP_REQUIRE(J > 0 && n % J == 0, "%s: J=%d (> 0, dividing n_points=%lld)", fn, J, (long long)n);
-    }
-    MVP_REQUIRE(!std::isnan(min_conf), "%s: min_conf is NaN", fn);
-    MVP_REQUIRE(cov_floor >= 0.f, "%s: cov_floor=%g (not NaN, >= 0)", fn, (double)cov_floor);
-    MVP_REQUIRE(!std::isnan(huber_delta), "%s: huber_delta is NaN", fn);
+    c.obs = reproj_parse_obs(fn, kpts, n, V, mask, weights, gauss, J, min_conf, cov_floor, huber_delta);
     MVP_REQUIRE(!std::isnan(sigma), "%s: trans_prior_sigma is NaN", fn);
     MVP_REQUIRE(workspace_bytes >= c.pl.bytes, "%s: workspace_bytes=%lld < %lld needed (n_points=%lld, free_mask=0x%x)", fn,
                 (long long)workspace_bytes, (long long)c.pl.bytes, (long long)n, free_mask);
-    c.vw.cols = 0;
-    for (int j = 0; j < nv; j++) c.vw.cols |= (unsigned)ci.v[j] << (4 * j);
-    c.vw.free_mask = free_mask;
-    c.vw.nv = nv;
-    c.vw.F = c.pl.F;
-    c.obs = BaObsArgs{kpts, mask, gauss, n, V, weights, J, min_conf, cov_floor};
-    c.hub = huber_delta > 0 ? huber_delta : 0.0;
+    c.vw = BaViews{view_list(ci, nv), free_mask, c.pl.F};
     c.inv_s2 = sigma > 0 ? 1.0 / (sigma * sigma) : 0.0;
     return c;
 }
@@ -894,7 +797,6 @@ extern "C" int mvp_bundle_adjust_system(const float* kpts, int64_t n_points, int
     a.used = used;
     a.part = part;
     a.lambda = lambda;
-    a.hub = c.hub;
     ba_launch_linearise(c, a, s);
     hipLaunchKernelGGL(ba_assemble_kernel, dim3(1), dim3(kBaSolveBlock), 0, s, part, c.pl.lin_grid, c.pl.nr, c.pl.F, lambda,
                        c.inv_s2, out_S, out_b, out_cost, out_counts);
@@ -936,8 +838,7 @@ extern "C" int mvp_bundle_adjust(const float* kpts, int64_t n_points, int V, con
     a.x64 = x64;
     a.used = used;
     a.part = part;
-    a.hub = c.hub;
-    BaPtArgs pa{c.obs, c.vw, st, x64, used, tpart, c.hub};
+    BaPtArgs pa{c.obs, c.vw, st, x64, used, tpart};
     for (int it = 0; it < max_iter; it++) {
         ba_launch_linearise(c, a, s);
         hipLaunchKernelGGL(ba_solve_kernel, dim3(1), dim3(kBaSolveBlock), 0, s, st, part, c.pl.lin_grid, c.pl.nr, c.vw, cams,

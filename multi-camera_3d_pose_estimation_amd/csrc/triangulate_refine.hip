@@ -21,35 +21,27 @@ namespace {
 //   * ONE copy of the cost / gradient / Hessian evaluation inside the trial loop (trip 0 evaluates
 //     the seed); accept / reject is selects, and the loop is left on a wave ballot once every lane
 //     has converged, failed or used up max_iter — the pattern of triangulate_tol2_kernel.
-//   (RefineCam, the observation rule, the forward model and the 3x3 Cholesky are in refine_common.h,
-//   which the bundle adjustment shares.)
+//   (The observation rule, the forward model and the 3x3 Cholesky: refine_common.h, shared.)
 
 template <int NV>
 __global__ __launch_bounds__(kBlock) void triangulate_refine_kernel(
-    const float* __restrict__ kpts, int64_t n, int V, const double* __restrict__ cams, CamIdx ci,
-    const float* __restrict__ xyz0, const uint8_t* __restrict__ mask, int weights, const double* __restrict__ gauss,
-    int J, float min_conf, float cov_floor, int max_iter, double tol, float* __restrict__ out_xyz,
-    float* __restrict__ out_cov, float* __restrict__ out_cost, uint8_t* __restrict__ out_status) {
+    ReprojObs o, ViewList vl, const double* __restrict__ cams, const float* __restrict__ xyz0, int max_iter, double tol,
+    float* __restrict__ out_xyz, float* __restrict__ out_cov, float* __restrict__ out_cost,
+    uint8_t* __restrict__ out_status) {
 #pragma clang fp contract(fast)
     __shared__ double s_zx[NV][kBlock], s_zy[NV][kBlock], s_wxx[NV][kBlock], s_wxy[NV][kBlock], s_wyy[NV][kBlock];
-    // the listed cameras (each < kMaxCams = 8) as nibbles of one scalar: the rolled view loop's index
-    unsigned cols = 0;
-#pragma unroll
-    for (int j = 0; j < NV; j++) cols |= (unsigned)ci.v[j] << (4 * j);
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
+    if (p >= o.n) return;
     const int tid = threadIdx.x;
-    const float* __restrict__ kp = kpts + p * 3 * V;
-    const unsigned allowed = mask ? (unsigned)mask[p] : 0xFFu;
-    const int64_t gt = (weights == MVP_REFINE_W_GAUSS) ? p / J : 0;
-    const int gj = (weights == MVP_REFINE_W_GAUSS) ? (int)(p % J) : 0;
+    const unsigned allowed = reproj_allowed(o, p);
+    int64_t gt;
+    int gj;
+    reproj_frame_joint(o, p, gt, gj);
     unsigned used = 0;
 #pragma unroll
     for (int j = 0; j < NV; j++) {
-        const int col = ci.v[j];
         double ox, oy, a, b, d;
-        const bool ok = refine_observation(kp, V, col, (allowed >> j) & 1u, weights, gauss, gt, gj, J, min_conf,
-                                           cov_floor, ox, oy, a, b, d);
+        const bool ok = reproj_observe(o, p, gt, gj, vl.col(j), (allowed >> j) & 1u, ox, oy, a, b, d);
         used |= (ok ? 1u : 0u) << j;
         s_zx[j][tid] = ok ? ox : 0.0;
         s_zy[j][tid] = ok ? oy : 0.0;
@@ -74,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void triangulate_refine_kernel(
         bool front = true;
 #pragma unroll 1
         for (int j = 0; j < NV; j++) {
-            const RefineCam c = refine_cam(cams + ((cols >> (4 * j)) & 15u) * MVP_CAM_DOUBLES);
+            const RefineCam c = refine_cam(cams + vl.col(j) * MVP_CAM_DOUBLES);
             double fj = 0, gj3[3] = {0, 0, 0}, Hj[6] = {0, 0, 0, 0, 0, 0};
             const bool infront = refine_view_terms(c, Xn, s_zx[j][tid], s_zy[j][tid], s_wxx[j][tid], s_wxy[j][tid],
                                                    s_wyy[j][tid], fj, gj3, Hj);
@@ -162,25 +154,16 @@ extern "C" int mvp_triangulate_refine(const float* kpts, int64_t n_points, int V
     MVP_ABI_BEGIN
     const char* fn = "mvp_triangulate_refine";
     const CamIdx ci = tri_parse_args(fn, n_points, V, n_cams, cam_idx, n_cam_idx);
-    MVP_REQUIRE(weights >= MVP_REFINE_W_UNIT && weights <= MVP_REFINE_W_GAUSS,
-                "mvp_triangulate_refine: weights=%d (0..2)", weights);
-    if (weights == MVP_REFINE_W_GAUSS) {
-        MVP_REQUIRE(gauss != nullptr, "mvp_triangulate_refine: MVP_REFINE_W_GAUSS needs gauss_dev");
-        MVP_REQUIRE(J > 0 && n_points % J == 0, "mvp_triangulate_refine: J=%d (> 0, dividing n_points=%lld)", J,
-                    (long long)n_points);
-    }
-    MVP_REQUIRE(!std::isnan(min_conf), "mvp_triangulate_refine: min_conf is NaN");
-    MVP_REQUIRE(cov_floor >= 0.f, "mvp_triangulate_refine: cov_floor=%g (not NaN, >= 0)", (double)cov_floor);
-    MVP_REQUIRE(max_iter >= 0 && max_iter <= 63, "mvp_triangulate_refine: max_iter=%d (0..63)", max_iter);
-    MVP_REQUIRE(std::isfinite(tol) && tol > 0, "mvp_triangulate_refine: tol=%g (finite, > 0)", tol);
+    const ReprojObs o = reproj_parse_obs(fn, kpts, n_points, V, mask, weights, gauss, J, min_conf, cov_floor, 0.0);
+    MVP_REQUIRE(max_iter >= 0 && max_iter <= 63, "%s: max_iter=%d (0..63)", fn, max_iter);
+    MVP_REQUIRE(std::isfinite(tol) && tol > 0, "%s: tol=%g (finite, > 0)", fn, tol);
     if (n_points == 0) return MVP_OK;
-    MVP_REQUIRE(kpts && cams && xyz0 && out_xyz, "mvp_triangulate_refine: null device pointer");
+    MVP_REQUIRE(kpts && cams && xyz0 && out_xyz, "%s: null device pointer", fn);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const dim3 grid(tri_grid(fn, n_points)), block(kBlock);
     tri_dispatch_views(n_cam_idx, [&](auto nv) {
-        hipLaunchKernelGGL((triangulate_refine_kernel<decltype(nv)::value>), grid, block, 0, s, kpts, n_points, V, cams,
-                           ci, xyz0, mask, weights, gauss, J, min_conf, cov_floor, max_iter, tol, out_xyz, out_cov,
-                           out_cost, out_status);
+        hipLaunchKernelGGL((triangulate_refine_kernel<decltype(nv)::value>), grid, block, 0, s, o, view_list(ci, n_cam_idx),
+                           cams, xyz0, max_iter, tol, out_xyz, out_cov, out_cost, out_status);
     });
     MVP_HIP(hipGetLastError());
     MVP_ABI_END

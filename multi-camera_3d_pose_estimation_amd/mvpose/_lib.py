@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MVPOSE_LIB", os.path.join(_HERE, "libmvpose.so"))
 
@@ -164,6 +166,16 @@ if lib.mvp_abi_version() != ABI_VERSION:
 
 def last_error() -> str:
     return lib.mvp_last_error().decode(errors="replace")
+
+
+def ptr(t):
+    """A tensor's device pointer as the C-ABI takes it; None stays None (an optional argument)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream(device=None) -> ctypes.c_void_p:
+    """The current HIP stream of `device`: every call is enqueued on it."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def call(name: str, *args) -> None:

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import geometry
-from ._lib import call
+from ._lib import call, ptr, stream
 from .hrnet import HEATMAP_HW, INPUT_HW, N_JOINTS, HRNetBackbone
 
 MEAN = np.array([123.675, 116.28, 103.53], np.float32)   # PoseDataPreprocessor (RGB order)
@@ -37,14 +37,6 @@ def warp_is_separable(minv, img_h, img_w) -> bool:
     call("mvp_warp_is_separable", m.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(img_h), int(img_w),
          ctypes.byref(out))
     return bool(out.value)
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 class BatchPoseEstimator:
@@ -134,9 +126,9 @@ class BatchPoseEstimator:
         if bx.shape[0] != n:
             raise ValueError(f"bboxes: {bx.shape[0]} boxes for {n} frames")
         cm, rm, cs, sep = (t[:n] for t in self._geo_dev[k])
-        call("mvp_bbox_geometry", _ptr(bx), int(bx.shape[1]), n, score_col,
-             ctypes.c_float(0.0 if bbox_thr is None else float(bbox_thr)), self.frame_h, self.frame_w, _ptr(cm),
-             _ptr(rm), _ptr(cs), _ptr(sep), _stream(self.device))
+        call("mvp_bbox_geometry", ptr(bx), int(bx.shape[1]), n, score_col,
+             ctypes.c_float(0.0 if bbox_thr is None else float(bbox_thr)), self.frame_h, self.frame_w, ptr(cm),
+             ptr(rm), ptr(cs), ptr(sep), stream(self.device))
         return cm, rm, cs, sep
 
     def run(self, frames: torch.Tensor, n_views: int = 1, kpts_tkv: torch.Tensor | None = None,
@@ -158,7 +150,7 @@ class BatchPoseEstimator:
             raise ValueError(f"frames must be (N, {self.frame_h}, {self.frame_w}, 3), got {tuple(frames.shape)}")
         if n > self.max_frames:
             raise ValueError(f"{n} frames > max_frames {self.max_frames}")
-        dev, s = self.device, _stream(self.device)
+        dev, s = self.device, stream(self.device)
         nc = n * (2 if self.flip_test else 1)
         crops = self.crops[:nc]
         k = self._avg_k ^ 1
@@ -172,8 +164,8 @@ class BatchPoseEstimator:
                 self._avg_busy[k] = None
             crop_minv, revert_minv, center_scale, sep_flags = self._bbox_geometry(k, n, bboxes, bbox_thr)
             separable = 1
-        call("mvp_preprocess", _ptr(frames), n, h, w, _ptr(crop_minv), INPUT_HW[0], INPUT_HW[1], self._mean,
-             self._std, int(self.swap_rb), int(self.flip_test), _ptr(crops), s)
+        call("mvp_preprocess", ptr(frames), n, h, w, ptr(crop_minv), INPUT_HW[0], INPUT_HW[1], self._mean,
+             self._std, int(self.swap_rb), int(self.flip_test), ptr(crops), s)
         hm = self.backbone.forward(crops, out=self.heatmaps[:nc])
         kp = torch.empty((n, N_JOINTS, 2), dtype=torch.float32, device=dev)
         sc = torch.empty((n, N_JOINTS), dtype=torch.float32, device=dev)
@@ -183,9 +175,9 @@ class BatchPoseEstimator:
             self._avg_busy[k] = None
         self._avg_k = k
         avg = self._avg[k][:n]
-        call("mvp_heatmap_decode", _ptr(hm[:n]), _ptr(hm[n:]) if self.flip_test else None, n, N_JOINTS,
-             HEATMAP_HW[0], HEATMAP_HW[1], self._flip, 1, _ptr(center_scale), INPUT_HW[1], INPUT_HW[0],
-             _ptr(avg), _ptr(kp), _ptr(sc), _ptr(am), _ptr(kpts_tkv), int(n_views), s)
+        call("mvp_heatmap_decode", ptr(hm[:n]), ptr(hm[n:]) if self.flip_test else None, n, N_JOINTS,
+             HEATMAP_HW[0], HEATMAP_HW[1], self._flip, 1, ptr(center_scale), INPUT_HW[1], INPUT_HW[0],
+             ptr(avg), ptr(kp), ptr(sc), ptr(am), ptr(kpts_tkv), int(n_views), s)
         gauss = torch.empty((n, N_JOINTS, 6), dtype=torch.float64, device=dev)
         done = None
         if overlap_moments:
@@ -198,8 +190,8 @@ class BatchPoseEstimator:
             gauss.record_stream(self._side)
         else:
             ms = s
-        call("mvp_heatmap_moments", _ptr(avg), n, N_JOINTS, HEATMAP_HW[0], HEATMAP_HW[1], _ptr(revert_minv),
-             h, w, ctypes.c_float(HEATMAP_THR), separable, _ptr(sep_flags), _ptr(gauss), ms)
+        call("mvp_heatmap_moments", ptr(avg), n, N_JOINTS, HEATMAP_HW[0], HEATMAP_HW[1], ptr(revert_minv),
+             h, w, ctypes.c_float(HEATMAP_THR), separable, ptr(sep_flags), ptr(gauss), ms)
         if overlap_moments:
             done = torch.cuda.Event()
             done.record(self._side)
@@ -217,8 +209,8 @@ class BatchPoseEstimator:
         minv = self._last_revert[index:index + 1]
         src = self.avg[index:index + 1].contiguous()
         out = torch.empty((1, N_JOINTS, self.frame_h, self.frame_w), dtype=torch.float32, device=self.device)
-        call("mvp_heatmap_revert", _ptr(src), 1, N_JOINTS, HEATMAP_HW[0], HEATMAP_HW[1], _ptr(minv), self.frame_h,
-             self.frame_w, _ptr(out), _stream(self.device))
+        call("mvp_heatmap_revert", ptr(src), 1, N_JOINTS, HEATMAP_HW[0], HEATMAP_HW[1], ptr(minv), self.frame_h,
+             self.frame_w, ptr(out), stream(self.device))
         return out[0].cpu().numpy()
 
     @staticmethod

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call
+from ._lib import call, ptr, stream
 
 BN_EPS = 1e-5
 STAGES = ((1, (32, 64)), (4, (32, 64, 128)), (3, (32, 64, 128, 256)))
@@ -600,9 +600,8 @@ class ConvGraph:
         with torch.cuda.device(self.device):
             segs = (ctypes.c_int * len(spec.seg_micro_batch))(*spec.seg_micro_batch)
             call("mvp_graph_create", tens, len(spec.tensors), ops, len(spec.ops), segs, len(spec.seg_micro_batch),
-                 self.input_id, self.output_id,
-                 ctypes.c_void_p(self.w_dev.data_ptr()), self.w_dev.numel(), ctypes.c_void_p(self.f_dev.data_ptr()),
-                 self.f_dev.numel(), self.max_batch, ctypes.byref(h))
+                 self.input_id, self.output_id, ptr(self.w_dev), self.w_dev.numel(), ptr(self.f_dev), self.f_dev.numel(),
+                 self.max_batch, ctypes.byref(h))
         self._h = h
 
     def run(self, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -610,8 +609,7 @@ class ConvGraph:
         n = x.shape[0]
         if n > self.max_batch:
             raise ValueError(f"batch {n} > max_batch {self.max_batch}")
-        call("mvp_graph_forward", self._h, ctypes.c_void_p(x.data_ptr()), n, ctypes.c_void_p(out.data_ptr()),
-             ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
+        call("mvp_graph_forward", self._h, ptr(x), n, ptr(out), stream(x.device))
         return out
 
     def refresh_weights(self) -> None:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call
+from ._lib import call, ptr, stream
 
 CAM_DOUBLES = 40
 TRI_REFERENCE = 0
@@ -25,14 +25,6 @@ REFINE_W_UNIT = 0        # mvp_triangulate_refine weights (mvpose.h MVP_REFINE_W
 REFINE_W_CONF = 1
 REFINE_W_GAUSS = 2
 REFINE_WEIGHTS = {"unit": REFINE_W_UNIT, "conf": REFINE_W_CONF, "heatmap": REFINE_W_GAUSS}
-
-
-def _stream(device=None) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _ptr(t: torch.Tensor) -> ctypes.c_void_p:
-    return ctypes.c_void_p(t.data_ptr())
 
 
 def _require(t: torch.Tensor, dtype, name: str):
@@ -72,6 +64,46 @@ def _unpack_view_bits(bits: torch.Tensor, nv: int) -> torch.Tensor:
     """_pack_view_bits' inverse: (...) uint8 -> (..., nv) bool."""
     shifts = torch.arange(nv, dtype=torch.uint8, device=bits.device)
     return ((bits.unsqueeze(-1) >> shifts) & 1).to(torch.bool)
+
+
+def _obs_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, *, xyz_name="xyz", frames=False,
+              free=None):
+    """Shared front of the reprojection-error solvers (triangulate_refine, bundle_adjust*,
+    trajectory_fit*, skeleton_fit*): the checks of kpts (..., 3, V), cams, cam_idx, xyz (..., 3),
+    weights, gauss (T, V, J, 6) and mask (..., NV), and the packed arguments.  frames: kpts must be
+    (T, P, 3, V), and the C call takes T, P in place of the point count and no J (the fits); free: the
+    view positions whose bit mask follows n_cam_idx (the bundle adjustment).  Returns (lead, the number of
+    points, nv, args, bits): args is the C call's leading arguments, kpts_dev .. cov_floor; bits is the
+    packed mask that args points into, which the caller holds until it has made the call."""
+    if weights not in REFINE_WEIGHTS:
+        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
+    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
+    if frames and len(lead) != 2:
+        raise ValueError(f"kpts must be (T, P, 3, V), got {tuple(kpts.shape)}")
+    nv = len(ci)
+    _require(xyz, torch.float32, xyz_name)
+    if tuple(xyz.shape) != lead + (3,):
+        raise ValueError(f"{xyz_name} must be {lead + (3,)}, got {tuple(xyz.shape)}")
+    J = 0
+    if weights == "heatmap":
+        if gauss is None:
+            raise ValueError('weights="heatmap" needs gauss, the (T, V, J, 6) float64 heatmap Gaussians')
+        _require(gauss, torch.float64, "gauss")
+        if len(lead) != 2 or tuple(gauss.shape) != (lead[0], V, lead[1], 6):
+            raise ValueError(f"gauss must be (T, V, J, 6) = {(lead[0] if lead else None, V, lead[-1] if lead else None, 6)} "
+                             f"for kpts (T, J, 3, V), got {tuple(gauss.shape)}")
+        J = lead[1]
+    bits = None
+    if mask is not None:
+        _require(mask, torch.bool, "mask")
+        if tuple(mask.shape) != lead + (nv,):
+            raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
+        bits = _pack_view_bits(mask)
+    args = ((ptr(kpts),) + ((int(lead[0]), int(lead[1])) if frames else (n,)) + (V, ptr(cams), cams.shape[0], ci, nv)
+            + (() if free is None else (_free_mask(free),))
+            + (ptr(xyz), ptr(bits), REFINE_WEIGHTS[weights], ptr(gauss) if weights == "heatmap" else None)
+            + (() if frames else (int(J),)) + (float(min_conf), float(cov_floor)))
+    return lead, n, nv, args, bits
 
 
 def pack_camera(K, R, T, dist) -> np.ndarray:
@@ -137,8 +169,8 @@ def triangulate(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int] =
         if tuple(out.shape) != lead + (3,):
             raise ValueError("out has the wrong shape")
     xyzw = torch.empty(lead + (4,), dtype=torch.float64, device=kpts.device) if return_xyzw else None
-    call("mvp_triangulate", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, len(ci), int(mode),
-         _ptr(out), _ptr(xyzw) if xyzw is not None else None, _stream(kpts.device))
+    call("mvp_triangulate", ptr(kpts), n, V, ptr(cams), cams.shape[0], ci, len(ci), int(mode),
+         ptr(out), ptr(xyzw), stream(kpts.device))
     return (out, xyzw) if return_xyzw else out
 
 
@@ -159,8 +191,8 @@ def triangulate_robust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
     bits = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
     err = torch.empty(lead + (nv,), dtype=torch.float32, device=kpts.device) if return_err else None
-    call("mvp_triangulate_robust", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
-         float(min_conf), _ptr(out), _ptr(bits), _ptr(err) if err is not None else None, _stream(kpts.device))
+    call("mvp_triangulate_robust", ptr(kpts), n, V, ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
+         float(min_conf), ptr(out), ptr(bits), ptr(err), stream(kpts.device))
     return out, _unpack_view_bits(bits, nv), err
 
 
@@ -182,36 +214,14 @@ def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     seed that is not finite or behind a camera) returns its seed, NaN cov and cost.  With equal
     isotropic noise in every view this does not beat the DLT seed: the gain is in the weighting
     and in the covariance."""
-    if weights not in REFINE_WEIGHTS:
-        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
-    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
-    _require(xyz0, torch.float32, "xyz0")
-    nv = len(ci)
-    if tuple(xyz0.shape) != lead + (3,):
-        raise ValueError(f"xyz0 must be {lead + (3,)}, got {tuple(xyz0.shape)}")
-    J = 0
-    if weights == "heatmap":
-        if gauss is None:
-            raise ValueError('weights="heatmap" needs gauss, the (T, V, J, 6) float64 heatmap Gaussians')
-        _require(gauss, torch.float64, "gauss")
-        if len(lead) != 2 or tuple(gauss.shape) != (lead[0], V, lead[1], 6):
-            raise ValueError(f"gauss must be (T, V, J, 6) = {(lead[0] if lead else None, V, lead[-1] if lead else None, 6)} "
-                             f"for kpts (T, J, 3, V), got {tuple(gauss.shape)}")
-        J = lead[1]
-    bits = None
-    if mask is not None:
-        _require(mask, torch.bool, "mask")
-        if tuple(mask.shape) != lead + (nv,):
-            raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
-        bits = _pack_view_bits(mask)
+    lead, _, _, args, _bits = _obs_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask, min_conf, cov_floor,
+                                        xyz_name="xyz0")
     out = torch.empty(lead + (3,), dtype=torch.float32, device=kpts.device)
     cov6 = torch.empty(lead + (6,), dtype=torch.float32, device=kpts.device)
     cost = torch.empty(lead, dtype=torch.float32, device=kpts.device)
     status = torch.empty(lead, dtype=torch.uint8, device=kpts.device)
-    call("mvp_triangulate_refine", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor), int(max_iter),
-         float(tol), _ptr(out), _ptr(cov6), _ptr(cost), _ptr(status), _stream(kpts.device))
+    call("mvp_triangulate_refine", *args, int(max_iter), float(tol), ptr(out), ptr(cov6), ptr(cost), ptr(status),
+         stream(kpts.device))
     sym = torch.tensor([0, 1, 2, 1, 3, 4, 2, 4, 5], device=kpts.device)
     cov = cov6.index_select(-1, sym).reshape(lead + (3, 3))
     return out, cov, cost, status
@@ -221,7 +231,7 @@ def triangulate_fallback_total(device=None) -> int:
     """Points the MVP_TRI_TOLERANCE solver has re-solved on the exact path on the current stream
     so far (mvp_triangulate_fallback_total; synchronises the stream)."""
     out = ctypes.c_ulonglong(0)
-    call("mvp_triangulate_fallback_total", _stream(device), ctypes.byref(out))
+    call("mvp_triangulate_fallback_total", stream(device), ctypes.byref(out))
     return int(out.value)
 
 
@@ -239,8 +249,8 @@ def triangulate_points_f64(kpts: torch.Tensor, cams: torch.Tensor, return_xyzw: 
     n = int(np.prod(lead)) if lead else 1
     out = torch.empty(lead + (3,), dtype=torch.float64, device=kpts.device)
     xyzw = torch.empty(lead + (4,), dtype=torch.float64, device=kpts.device) if return_xyzw else None
-    call("mvp_triangulate_points_f64", _ptr(kpts), n, _ptr(cams), _ptr(out),
-         _ptr(xyzw) if xyzw is not None else None, _stream(kpts.device))
+    call("mvp_triangulate_points_f64", ptr(kpts), n, ptr(cams), ptr(out),
+         ptr(xyzw), stream(kpts.device))
     return (out, xyzw) if return_xyzw else out
 
 
@@ -271,13 +281,17 @@ def _smooth_inputs(xyz, cov, valid):
     return T, P, cov6, v8
 
 
+def _plan3(name: str, *ints):
+    """A *_plan call of the time-parallel solvers: (chunk used, chunks per chain, workspace bytes)."""
+    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
+    call(name, *[int(i) for i in ints], ctypes.byref(used), ctypes.byref(n_chunks), ctypes.byref(nbytes))
+    return used.value, n_chunks.value, nbytes.value
+
+
 def trajectory_smooth_plan(T: int, P: int, chunk: int = 0):
     """What trajectory_smooth will use for (T, P, chunk) (mvp_trajectory_smooth_plan): the chunk
     length, the chunks per chain and the workspace bytes."""
-    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("mvp_trajectory_smooth_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
-         ctypes.byref(nbytes))
-    return used.value, n_chunks.value, nbytes.value
+    return _plan3("mvp_trajectory_smooth_plan", T, P, chunk)
 
 
 def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid: torch.Tensor | None = None, *,
@@ -305,20 +319,16 @@ def trajectory_smooth(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid:
     resid = torch.empty((T, P), dtype=torch.float32, device=dev) if want_resid else None
     observed = torch.empty((T, P), dtype=torch.uint8, device=dev) if want_observed else None
     status = torch.empty((P,), dtype=torch.uint8, device=dev) if want_status else None
-    opt = (lambda t: _ptr(t) if t is not None else None)
-    call("mvp_trajectory_smooth", _ptr(xyz), opt(cov6), opt(v8), T, P, float(lambda_smooth), float(sigma0),
-         float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(resid), opt(observed), opt(status),
-         _stream(dev))
+    call("mvp_trajectory_smooth", ptr(xyz), ptr(cov6), ptr(v8), T, P, float(lambda_smooth), float(sigma0),
+         float(cov_floor), int(chunk), ptr(work), int(nbytes), ptr(out), ptr(resid), ptr(observed), ptr(status),
+         stream(dev))
     return out, resid, observed.to(torch.bool) if observed is not None else None, status
 
 
 def trajectory_smooth_cov_plan(T: int, P: int, chunk: int = 0):
     """What trajectory_smooth_cov will use for (T, P, chunk) (mvp_trajectory_smooth_cov_plan): the
     chunk length, the chunks per chain and the workspace bytes."""
-    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("mvp_trajectory_smooth_cov_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
-         ctypes.byref(nbytes))
-    return used.value, n_chunks.value, nbytes.value
+    return _plan3("mvp_trajectory_smooth_cov_plan", T, P, chunk)
 
 
 def trajectory_smooth_cov(xyz: torch.Tensor, cov: torch.Tensor | None = None, valid: torch.Tensor | None = None, *,
@@ -339,9 +349,8 @@ def trajectory_smooth_cov(xyz: torch.Tensor, cov: torch.Tensor | None = None, va
     out = torch.empty((T, P, 6), dtype=torch.float32, device=dev)
     cross = torch.empty((T, P, 3, 3), dtype=torch.float32, device=dev) if want_cross else None
     status = torch.empty((P,), dtype=torch.uint8, device=dev) if want_status else None
-    opt = (lambda t: _ptr(t) if t is not None else None)
-    call("mvp_trajectory_smooth_cov", _ptr(xyz), opt(cov6), opt(v8), T, P, float(lambda_smooth), float(sigma0),
-         float(cov_floor), int(chunk), _ptr(work), int(nbytes), _ptr(out), opt(cross), opt(status), _stream(dev))
+    call("mvp_trajectory_smooth_cov", ptr(xyz), ptr(cov6), ptr(v8), T, P, float(lambda_smooth), float(sigma0),
+         float(cov_floor), int(chunk), ptr(work), int(nbytes), ptr(out), ptr(cross), ptr(status), stream(dev))
     return out, cross, status
 
 
@@ -379,8 +388,8 @@ def epipolar_lag_cost(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[
     nl = 2 * int(max_lag) + 1
     out_sum = torch.empty((len(pairs), nl), dtype=torch.float64, device=dev)
     out_cnt = torch.empty((len(pairs), nl), dtype=torch.int64, device=dev)
-    call("mvp_epipolar_lag_cost", _ptr(kpts), T, J, V, _ptr(cams), cams.shape[0], ci, nv, int(max_lag),
-         float(min_conf), float(trunc_px), _ptr(work), int(nbytes), _ptr(out_sum), _ptr(out_cnt), _stream(dev))
+    call("mvp_epipolar_lag_cost", ptr(kpts), T, J, V, ptr(cams), cams.shape[0], ci, nv, int(max_lag),
+         float(min_conf), float(trunc_px), ptr(work), int(nbytes), ptr(out_sum), ptr(out_cnt), stream(dev))
     return out_sum, out_cnt, pairs
 
 
@@ -424,9 +433,9 @@ def associate_views(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[in
     group = torch.empty((T, nv, P), dtype=torch.int8, device=dev)
     count = torch.empty((T, 2), dtype=torch.uint8, device=dev)
     aff = torch.empty((T, len(pairs), P, P), dtype=torch.float64, device=dev) if return_affinity else None
-    call("mvp_associate_views", _ptr(kpts), T, P, J, V, _ptr(cams), cams.shape[0], ci, nv, float(min_conf),
-         float(trunc_px), float(max_cost_px), int(min_joints), _ptr(work), int(nbytes), _ptr(group), _ptr(count),
-         _ptr(aff) if aff is not None else None, _stream(dev))
+    call("mvp_associate_views", ptr(kpts), T, P, J, V, ptr(cams), cams.shape[0], ci, nv, float(min_conf),
+         float(trunc_px), float(max_cost_px), int(min_joints), ptr(work), int(nbytes), ptr(group), ptr(count),
+         ptr(aff), stream(dev))
     return group, count, aff, pairs
 
 
@@ -465,9 +474,9 @@ def track_people(xyz: torch.Tensor, *, max_gap: int = 5, max_jump: float = 50.0,
     n_tracks = torch.empty(lead[:-2], dtype=torch.int32, device=dev)
     cost = torch.empty(lead, dtype=torch.float64, device=dev) if return_links else None
     lag = torch.empty(lead, dtype=torch.uint8, device=dev) if return_links else None
-    call("mvp_track_people", _ptr(xyz), M, T, G, J, int(max_gap), float(max_jump), float(gap_growth), int(min_joints),
-         _ptr(track), _ptr(n_tracks), _ptr(cost) if return_links else None, _ptr(lag) if return_links else None,
-         _stream(dev))
+    call("mvp_track_people", ptr(xyz), M, T, G, J, int(max_gap), float(max_jump), float(gap_growth), int(min_joints),
+         ptr(track), ptr(n_tracks), ptr(cost) if return_links else None, ptr(lag) if return_links else None,
+         stream(dev))
     return track, n_tracks, cost, lag
 
 
@@ -493,32 +502,6 @@ def bundle_adjust_plan(n_points: int, nv: int, free: Sequence[int]) -> int:
     return nbytes.value
 
 
-def _ba_args(kpts, cams, cam_idx, free, xyz, weights, gauss, mask):
-    """Shared front of the two bundle-adjustment calls: checks and the packed arguments."""
-    if weights not in REFINE_WEIGHTS:
-        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
-    V, lead, n, ci = _tri_args(kpts, cams, cam_idx)
-    nv = len(ci)
-    _require(xyz, torch.float32, "xyz")
-    if tuple(xyz.shape) != lead + (3,):
-        raise ValueError(f"xyz must be {lead + (3,)}, got {tuple(xyz.shape)}")
-    J = 0
-    if weights == "heatmap":
-        if gauss is None:
-            raise ValueError('weights="heatmap" needs gauss, the (T, V, J, 6) float64 heatmap Gaussians')
-        _require(gauss, torch.float64, "gauss")
-        if len(lead) != 2 or tuple(gauss.shape) != (lead[0], V, lead[1], 6):
-            raise ValueError(f"gauss must be (T, V, J, 6) for kpts (T, J, 3, V), got {tuple(gauss.shape)}")
-        J = lead[1]
-    bits = None
-    if mask is not None:
-        _require(mask, torch.bool, "mask")
-        if tuple(mask.shape) != lead + (nv,):
-            raise ValueError(f"mask must be {lead + (nv,)}, got {tuple(mask.shape)}")
-        bits = _pack_view_bits(mask)
-    return V, lead, n, ci, nv, J, bits, _free_mask(free)
-
-
 def bundle_adjust_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], free: Sequence[int],
                          xyz: torch.Tensor, *, lam: float = 0.0, weights: str = "unit",
                          gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None, min_conf: float = 0.0,
@@ -530,21 +513,17 @@ def bundle_adjust_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequen
     positions in cam_idx of the views whose R, T are unknowns (F of them, at least one view stays
     fixed).  Returns (S (6F, 6F) float64, b (6F,) float64, cost () float64, counts (2,) int64:
     active points and their used views), all on the GPU."""
-    V, lead, n, ci, nv, J, bits, fm = _ba_args(kpts, cams, cam_idx, free, xyz, weights, gauss, mask)
-    nbytes = ctypes.c_int64(0)
-    call("mvp_bundle_adjust_plan", n, nv, fm, ctypes.byref(nbytes))
+    lead, n, nv, args, _bits = _obs_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, free=free)
+    nbytes = bundle_adjust_plan(n, nv, free)
     dev = kpts.device
-    n6 = 6 * bin(fm).count("1")
-    work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    n6 = 6 * bin(_free_mask(free)).count("1")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     S = torch.empty((n6, n6), dtype=torch.float64, device=dev)
     b = torch.empty((n6,), dtype=torch.float64, device=dev)
     cost = torch.empty((), dtype=torch.float64, device=dev)
     counts = torch.empty((2,), dtype=torch.int64, device=dev)
-    call("mvp_bundle_adjust_system", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, fm, _ptr(xyz),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor),
-         float(huber_delta), float(trans_prior_sigma), float(lam), _ptr(work), nbytes.value, _ptr(S), _ptr(b),
-         _ptr(cost), _ptr(counts), _stream(dev))
+    call("mvp_bundle_adjust_system", *args, float(huber_delta), float(trans_prior_sigma), float(lam), ptr(work), nbytes,
+         ptr(S), ptr(b), ptr(cost), ptr(counts), stream(dev))
     return S, b, cost, counts
 
 
@@ -562,59 +541,34 @@ def bundle_adjust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int]
     replaced; xyz (..., 3) float32; point_status (...) uint8: 0x80 for a point that took no part
     and is returned as its seed; cam_cov (6F, 6F) float64 over (dw, du) per free view in ascending
     position; info (8,) float64: BA_INFO_FIELDS), all on the GPU."""
-    V, lead, n, ci, nv, J, bits, fm = _ba_args(kpts, cams, cam_idx, free, xyz0, weights, gauss, mask)
-    nbytes = ctypes.c_int64(0)
-    call("mvp_bundle_adjust_plan", n, nv, fm, ctypes.byref(nbytes))
+    lead, n, nv, args, _bits = _obs_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask, min_conf, cov_floor,
+                                         free=free)
+    nbytes = bundle_adjust_plan(n, nv, free)
     dev = kpts.device
-    n6 = 6 * bin(fm).count("1")
-    work = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    n6 = 6 * bin(_free_mask(free)).count("1")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out_cams = torch.empty_like(cams)
     out = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
     status = torch.empty(lead, dtype=torch.uint8, device=dev)
     cov = torch.empty((n6, n6), dtype=torch.float64, device=dev)
     info = torch.empty((8,), dtype=torch.float64, device=dev)
-    call("mvp_bundle_adjust", _ptr(kpts), n, V, _ptr(cams), cams.shape[0], ci, nv, fm, _ptr(xyz0),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, int(J), float(min_conf), float(cov_floor),
-         float(huber_delta), float(trans_prior_sigma), int(max_iter), float(tol), _ptr(work), nbytes.value,
-         _ptr(out_cams), _ptr(out), _ptr(status), _ptr(cov), _ptr(info), _stream(dev))
+    call("mvp_bundle_adjust", *args, float(huber_delta), float(trans_prior_sigma), int(max_iter), float(tol), ptr(work),
+         nbytes, ptr(out_cams), ptr(out), ptr(status), ptr(cov), ptr(info), stream(dev))
     return out_cams, out, status, cov, info
 
 
 def trajectory_fit_plan(T: int, P: int, chunk: int = 0):
     """What trajectory_fit will use for (T, P, chunk) (mvp_trajectory_fit_plan): the chunk length
     of its time-parallel solve, the chunks per chain and the workspace bytes."""
-    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("mvp_trajectory_fit_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
-         ctypes.byref(nbytes))
-    return used.value, n_chunks.value, nbytes.value
+    return _plan3("mvp_trajectory_fit_plan", T, P, chunk)
 
 
-def _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask):
-    """Shared front of the two trajectory-fit calls: checks and the packed arguments."""
-    if weights not in REFINE_WEIGHTS:
-        raise ValueError(f"weights {weights!r}: one of {tuple(REFINE_WEIGHTS)}")
-    V, lead, _, ci = _tri_args(kpts, cams, cam_idx)
-    if len(lead) != 2:
-        raise ValueError(f"kpts must be (T, P, 3, V), got {tuple(kpts.shape)}")
-    T, P = int(lead[0]), int(lead[1])
-    nv = len(ci)
-    _require(xyz, torch.float32, "xyz")
-    if tuple(xyz.shape) != (T, P, 3):
-        raise ValueError(f"xyz must be {(T, P, 3)}, got {tuple(xyz.shape)}")
-    if weights == "heatmap":
-        if gauss is None:
-            raise ValueError('weights="heatmap" needs gauss, the (T, V, P, 6) float64 heatmap Gaussians')
-        _require(gauss, torch.float64, "gauss")
-        if tuple(gauss.shape) != (T, V, P, 6):
-            raise ValueError(f"gauss must be {(T, V, P, 6)}, got {tuple(gauss.shape)}")
-    bits = None
-    if mask is not None:
-        _require(mask, torch.bool, "mask")
-        if tuple(mask.shape) != (T, P, nv):
-            raise ValueError(f"mask must be {(T, P, nv)}, got {tuple(mask.shape)}")
-        bits = _pack_view_bits(mask)
-    return V, T, P, ci, nv, bits
+def _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, huber_delta):
+    """Shared front of the trajectory-fit and skeleton-fit calls: (T, P, the C call's leading
+    arguments kpts_dev .. huber_delta, the packed mask to hold until the call is made)."""
+    (T, P), _, _, args, bits = _obs_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor,
+                                         frames=True)
+    return int(T), int(P), args + (float(huber_delta),), bits
 
 
 def trajectory_fit_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz: torch.Tensor, *,
@@ -629,16 +583,13 @@ def trajectory_fit_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Seque
     float64: Σ Jᵀ W̃ J per frame as (xx, xy, xz, yy, yz, zz); g (T, P, 3) float64: Σ Jᵀ W̃ r;
     nviews (T, P) uint8: used views; cost (P, 2) float64: Σ rho and ½ Σ |second difference|² per
     chain), all on the GPU."""
-    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, huber_delta)
     dev = kpts.device
     H = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
     g = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
     nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
     cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
-    call("mvp_trajectory_fit_system", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
-         _ptr(H), _ptr(g), _ptr(nviews), _ptr(cost), _stream(dev))
+    call("mvp_trajectory_fit_system", *args, ptr(H), ptr(g), ptr(nviews), ptr(cost), stream(dev))
     return H, g, nviews, cost
 
 
@@ -658,7 +609,7 @@ def trajectory_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int
     squared residual at the result, NaN without a used view; nviews (T, P) uint8; cost (P, 2)
     float64: the cost at the seed and at the result; status (P,) uint8: bits 0-5 the trials, 0x40
     not converged, 0x80 invalid chain (returned as its seed; NaN resid and cost)), all on the GPU."""
-    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask)
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask, min_conf, cov_floor, huber_delta)
     _, _, nbytes = trajectory_fit_plan(T, P, chunk)
     dev = kpts.device
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -667,21 +618,15 @@ def trajectory_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int
     nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
     cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
     status = torch.empty((P,), dtype=torch.uint8, device=dev)
-    call("mvp_trajectory_fit", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
-         float(lambda_smooth), int(max_iter), float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out),
-         _ptr(resid), _ptr(nviews), _ptr(cost), _ptr(status), _stream(dev))
+    call("mvp_trajectory_fit", *args, float(lambda_smooth), int(max_iter), float(tol), int(chunk), ptr(work),
+         int(nbytes), ptr(out), ptr(resid), ptr(nviews), ptr(cost), ptr(status), stream(dev))
     return out, resid, nviews, cost, status
 
 
 def trajectory_fit_cov_plan(T: int, P: int, chunk: int = 0):
     """What trajectory_fit_cov will use for (T, P, chunk) (mvp_trajectory_fit_cov_plan): the chunk
     length, the chunks per chain and the workspace bytes."""
-    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("mvp_trajectory_fit_cov_plan", int(T), int(P), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
-         ctypes.byref(nbytes))
-    return used.value, n_chunks.value, nbytes.value
+    return _plan3("mvp_trajectory_fit_cov_plan", T, P, chunk)
 
 
 def trajectory_fit_cov(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz: torch.Tensor, *,
@@ -697,28 +642,22 @@ def trajectory_fit_cov(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     Σ_{t,t+1}, row = coordinate of X_t, NaN at t = T−1, or None without want_cross; status (P,)
     uint8: 0, or 0x80 for an invalid chain, whose blocks are all NaN), in world units², all on the
     GPU.  Stream-ordered, no host synchronisation."""
-    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, huber_delta)
     _, _, nbytes = trajectory_fit_cov_plan(T, P, chunk)
     dev = kpts.device
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty((T, P, 6), dtype=torch.float32, device=dev)
     cross = torch.empty((T, P, 3, 3), dtype=torch.float32, device=dev) if want_cross else None
     status = torch.empty((P,), dtype=torch.uint8, device=dev)
-    call("mvp_trajectory_fit_cov", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
-         float(lambda_smooth), int(chunk), _ptr(work), int(nbytes), _ptr(out),
-         _ptr(cross) if cross is not None else None, _ptr(status), _stream(dev))
+    call("mvp_trajectory_fit_cov", *args, float(lambda_smooth), int(chunk), ptr(work), int(nbytes), ptr(out),
+         ptr(cross), ptr(status), stream(dev))
     return out, cross, status
 
 
 def skeleton_fit_plan(T: int, P: int, J: int, chunk: int = 0):
     """What skeleton_fit will use for (T, P, J, chunk) (mvp_skeleton_fit_plan): the chunk length of
     its time-parallel solve, the chunks per chain and the workspace bytes."""
-    used, n_chunks, nbytes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int64(0)
-    call("mvp_skeleton_fit_plan", int(T), int(P), int(J), int(chunk), ctypes.byref(used), ctypes.byref(n_chunks),
-         ctypes.byref(nbytes))
-    return used.value, n_chunks.value, nbytes.value
+    return _plan3("mvp_skeleton_fit_plan", T, P, J, chunk)
 
 
 def _skeleton_args(P, J, pairs, lengths, dev):
@@ -751,18 +690,15 @@ def skeleton_fit_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequenc
     arguments as for trajectory_fit_system.  Returns (H (T, P, 6) float64 and g (T, P, 3) float64:
     the data term plus the bone terms with lambda_bone applied; nviews (T, P) uint8; cost (G, 3)
     float64: Σ rho, ½ Σ |second difference|², ½ Σ (r − L)²), all on the GPU."""
-    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask)
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, huber_delta)
     dev = kpts.device
     J, G, seg, n_seg, ln = _skeleton_args(P, J, pairs, lengths, dev)
     H = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
     g = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
     nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
     cost = torch.empty((G, 3), dtype=torch.float64, device=dev)
-    call("mvp_skeleton_fit_system", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
-         J, seg, n_seg, _ptr(ln) if n_seg else None, float(lambda_bone), _ptr(H), _ptr(g), _ptr(nviews), _ptr(cost),
-         _stream(dev))
+    call("mvp_skeleton_fit_system", *args, J, seg, n_seg, ptr(ln) if n_seg else None, float(lambda_bone), ptr(H),
+         ptr(g), ptr(nviews), ptr(cost), stream(dev))
     return H, g, nviews, cost
 
 
@@ -782,7 +718,7 @@ def skeleton_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int],
     seed and at the result, the bone part of each; group_status (G,) uint8: bits 0-5 the trials, 0x40
     not converged, 0x80 invalid; chain_status (P,) uint8: 0x80 for a chain returned as its seed), all
     on the GPU."""
-    V, T, P, ci, nv, bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask)
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask, min_conf, cov_floor, huber_delta)
     dev = kpts.device
     J, G, seg, n_seg, ln = _skeleton_args(P, J, pairs, lengths, dev)
     _, _, nbytes = skeleton_fit_plan(T, P, J, chunk)
@@ -794,10 +730,7 @@ def skeleton_fit(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int],
     cost = torch.empty((G, 4), dtype=torch.float64, device=dev)
     gstatus = torch.empty((G,), dtype=torch.uint8, device=dev)
     cstatus = torch.empty((P,), dtype=torch.uint8, device=dev)
-    call("mvp_skeleton_fit", _ptr(kpts), T, P, V, _ptr(cams), cams.shape[0], ci, nv, _ptr(xyz0),
-         _ptr(bits) if bits is not None else None, REFINE_WEIGHTS[weights],
-         _ptr(gauss) if weights == "heatmap" else None, float(min_conf), float(cov_floor), float(huber_delta),
-         float(lambda_smooth), J, seg, n_seg, _ptr(ln) if n_seg else None, float(lambda_bone), int(max_iter),
-         float(tol), int(chunk), _ptr(work), int(nbytes), _ptr(out), _ptr(resid), _ptr(nviews), _ptr(bone), _ptr(cost),
-         _ptr(gstatus), _ptr(cstatus), _stream(dev))
+    call("mvp_skeleton_fit", *args, float(lambda_smooth), J, seg, n_seg, ptr(ln) if n_seg else None,
+         float(lambda_bone), int(max_iter), float(tol), int(chunk), ptr(work), int(nbytes), ptr(out), ptr(resid),
+         ptr(nviews), ptr(bone), ptr(cost), ptr(gstatus), ptr(cstatus), stream(dev))
     return out, resid, nviews, bone, cost, gstatus, cstatus

@@ -48,7 +48,7 @@ import torch
 
 from . import _lib
 from . import ops
-from ._lib import call
+from ._lib import call, ptr, stream
 
 CAM_FLOATS = 26
 N_COSTS = 4
@@ -78,14 +78,6 @@ _lib.lib.mvp_sgd_refine.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_v
                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                     ctypes.POINTER(SgdParams), ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 _PINNED = {}
@@ -197,8 +189,8 @@ def project_points_torch(points, K, R, T, dist_coeffs, indicies=None, torch_dtyp
     sel = pts[rows].reshape(-1, 3).to(dev).contiguous()
     cam = torch.from_numpy(camera_record(K, R, T, dist_coeffs)).to(dev)
     uv = torch.empty((sel.shape[0], 2), dtype=torch.float32, device=dev)
-    call("mvp_project_points", _ptr(sel), sel.shape[0], _ptr(cam), int(bool(ignore_distortions)), _ptr(uv),
-         _stream(dev))
+    call("mvp_project_points", ptr(sel), sel.shape[0], ptr(cam), int(bool(ignore_distortions)), ptr(uv),
+         stream(dev))
     return uv.reshape(len(rows), pts.shape[1], 2).to(home)
 
 
@@ -216,8 +208,8 @@ def linear_interpolation(points, k=5, k_std=2, median_std=2, use_rolling_average
         raise ValueError("points must be (time, n_points, dim) or (time, n_points)")
     out = torch.empty_like(x)
     T, P, D = x.shape
-    call("mvp_linear_interpolation", _ptr(x), T, P, D, int(k), float(k_std), float(median_std),
-         int(bool(use_rolling_average)), int(bool(filter_distance_from_median)), _ptr(out), _stream(dev))
+    call("mvp_linear_interpolation", ptr(x), T, P, D, int(k), float(k_std), float(median_std),
+         int(bool(use_rolling_average)), int(bool(filter_distance_from_median)), ptr(out), stream(dev))
     out = out[..., 0] if squeeze else out
     return out.to(home) if was_tensor else out.cpu().numpy()
 
@@ -489,8 +481,8 @@ def extrinsic_sample_grad(samples, targets, cam, n_samples, ignore_distortions=F
     if n_blocks is None:
         n_blocks = max(1, min(1024, (n_pts + 255) // 256))
     part = torch.empty((n_blocks, EXT_SUMS), dtype=torch.float64, device=samples.device)
-    call("mvp_extrinsic_sample_grad", _ptr(samples), _ptr(targets), int(n_samples), int(n_pts), _ptr(cam),
-         int(bool(ignore_distortions)), int(n_blocks), _ptr(part), _stream(samples.device))
+    call("mvp_extrinsic_sample_grad", ptr(samples), ptr(targets), int(n_samples), int(n_pts), ptr(cam),
+         int(bool(ignore_distortions)), int(n_blocks), ptr(part), stream(samples.device))
     return part.sum(0)
 
 
@@ -559,14 +551,14 @@ def refine_trajectories(gaussians, initial_trajectories, cameras, body_lengths=N
         slots = (ctypes.c_int * nl)(*[int(c) for c in learn_cams])
         cf = torch.empty((M, nl, 12), dtype=torch.float32, device=dev)
         cb = torch.full((M, nl, 12), float("nan"), dtype=torch.float32, device=dev)
-        call("mvp_sgd_refine_cams", _ptr(G), _ptr(X0), _ptr(cams), M, T, V, J, _ptr(seg), _ptr(seg_len), n_seg,
-             ctypes.byref(p), _ptr(ws), _ptr(final), _ptr(best), _ptr(batch_costs), _ptr(iter_means), _ptr(iters),
-             slots, nl, _ptr(cf), _ptr(cb), _stream(dev))
+        call("mvp_sgd_refine_cams", ptr(G), ptr(X0), ptr(cams), M, T, V, J, ptr(seg), ptr(seg_len), n_seg,
+             ctypes.byref(p), ptr(ws), ptr(final), ptr(best), ptr(batch_costs), ptr(iter_means), ptr(iters),
+             slots, nl, ptr(cf), ptr(cb), stream(dev))
         out["cams_final"], out["cams_best"] = cf, cb
     else:
-        call("mvp_sgd_refine", _ptr(G), _ptr(X0), _ptr(cams), M, T, V, J, _ptr(seg), _ptr(seg_len), n_seg,
-             ctypes.byref(p), _ptr(ws), _ptr(final), _ptr(best), _ptr(batch_costs), _ptr(iter_means), _ptr(iters),
-             _stream(dev))
+        call("mvp_sgd_refine", ptr(G), ptr(X0), ptr(cams), M, T, V, J, ptr(seg), ptr(seg_len), n_seg,
+             ctypes.byref(p), ptr(ws), ptr(final), ptr(best), ptr(batch_costs), ptr(iter_means), ptr(iters),
+             stream(dev))
     return out
 
 
@@ -879,13 +871,13 @@ class Optimized_3d_Pose_Estimation:
         n_pts = samples_3d.numel() // 3
         n_blocks = max(1, min(1024, (n_pts + 255) // 256))
         part = torch.empty((n_blocks, EXT_SUMS), dtype=torch.float64, device=dev)
-        s = _stream(dev)
+        s = stream(dev)
 
         def launch_step(step):
-            call("mvp_extrinsic_sample_grad", _ptr(samples_3d), _ptr(targets), int(N), int(n_pts), _ptr(cam),
-                 int(bool(ignore_distortions)), int(n_blocks), _ptr(part), s)
-            call("mvp_extrinsic_adam_step", _ptr(part), int(n_blocks), _ptr(cam), _ptr(state), float(lr),
-                 float(betas[0]), float(betas[1]), 1e-8, 1.0, _ptr(cost_hist), _ptr(param_hist), s)
+            call("mvp_extrinsic_sample_grad", ptr(samples_3d), ptr(targets), int(N), int(n_pts), ptr(cam),
+                 int(bool(ignore_distortions)), int(n_blocks), ptr(part), s)
+            call("mvp_extrinsic_adam_step", ptr(part), int(n_blocks), ptr(cam), ptr(state), float(lr),
+                 float(betas[0]), float(betas[1]), 1e-8, 1.0, ptr(cost_hist), ptr(param_hist), s)
 
         best_total = float("inf")
         no_improve = 0

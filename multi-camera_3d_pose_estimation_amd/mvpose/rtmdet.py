@@ -35,7 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call
+from ._lib import call, ptr, stream
 from .hrnet import TensorDesc, to_bf16_bits
 
 BN_EPS = 1e-5
@@ -530,8 +530,8 @@ class RTMDetector:
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             call("mvp_det_create", tens, len(self.spec.tensors), ops, len(self.spec.ops), input_id, self.size,
-                 self.n_priors, ctypes.c_void_p(self.w_dev.data_ptr()), self.w_dev.numel(),
-                 ctypes.c_void_p(self.f_dev.data_ptr()), self.f_dev.numel(), self.max_batch, ctypes.byref(h))
+                 self.n_priors, ptr(self.w_dev), self.w_dev.numel(), ptr(self.f_dev), self.f_dev.numel(), self.max_batch,
+                 ctypes.byref(h))
         self._h = h
         self.cand = torch.empty((self.max_batch, self.n_priors, 6), dtype=torch.float32, device=self.device)
         self.best = torch.empty((self.max_batch, 6), dtype=torch.float32, device=self.device)
@@ -573,17 +573,14 @@ class RTMDetector:
                                         not letterboxed.is_contiguous() or
                                         tuple(letterboxed.shape) != (n, self.size, self.size, 4)):
             raise ValueError(f"letterboxed must be a contiguous bfloat16 ({n}, {self.size}, {self.size}, 4) CUDA tensor")
-        lb = ctypes.c_void_p(letterboxed.data_ptr()) if letterboxed is not None else None
-        call("mvp_det_forward", self._h, ctypes.c_void_p(frames.data_ptr()), n, h, w,
-             ctypes.c_float(self.cfg["score_thr"]), ctypes.c_void_p(cand.data_ptr()),
-             ctypes.c_void_p(best.data_ptr()), lb, ctypes.c_void_p(torch.cuda.current_stream(frames.device).cuda_stream))
+        call("mvp_det_forward", self._h, ptr(frames), n, h, w, ctypes.c_float(self.cfg["score_thr"]), ptr(cand),
+             ptr(best), ptr(letterboxed), stream(frames.device))
         return {"best": best, "cand": cand, "frame_hw": (h, w)}
 
     # ---- layer-by-layer access (parity tests): mvp_det_run_ops / mvp_det_tensor_copy
     def run_ops(self, frames: torch.Tensor, begin: int, end: int) -> None:
         n, h, w = frames.shape[:3]
-        call("mvp_det_run_ops", self._h, ctypes.c_void_p(frames.data_ptr()), n, h, w, begin, end,
-             ctypes.c_void_p(self.cand.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        call("mvp_det_run_ops", self._h, ptr(frames), n, h, w, begin, end, ptr(self.cand), stream(self.device))
 
     def folded_ops(self) -> list[int]:
         """Per op: 1 when its pass runs inside its consumer conv (mvp_det_folded_ops)."""
@@ -604,15 +601,13 @@ class RTMDetector:
         """Overwrite arena tensor t's first len(x) images with x, (n, h, w, c) bf16."""
         h, w, c, _ = self.spec.tensors[t]
         assert x.dtype == torch.bfloat16 and tuple(x.shape[1:]) == (h, w, c) and x.is_contiguous(), x.shape
-        call("mvp_det_tensor_copy", self._h, t, x.shape[0], ctypes.c_void_p(x.data_ptr()), 1,
-             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        call("mvp_det_tensor_copy", self._h, t, x.shape[0], ptr(x), 1, stream(self.device))
 
     def tensor(self, t: int, n: int) -> torch.Tensor:
         """Copy of arena tensor t (first n images) as (n, h, w, c) bf16."""
         h, w, c, _ = self.spec.tensors[t]
         out = torch.empty((n, h, w, c), dtype=torch.bfloat16, device=self.device)
-        call("mvp_det_tensor_copy", self._h, t, n, ctypes.c_void_p(out.data_ptr()), 0,
-             ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        call("mvp_det_tensor_copy", self._h, t, n, ptr(out), 0, stream(self.device))
         return out
 
     @staticmethod
@@ -637,10 +632,9 @@ class RTMDetector:
         counts = torch.empty((n,), dtype=torch.int32, device=cand.device)
         fx, fy = self.scale_factors(*det["frame_hw"])
         offs = (ctypes.c_int * len(self.spec.level_off))(*self.spec.level_off)
-        call("mvp_det_nms", ctypes.c_void_p(cand.data_ptr()), n, self.n_priors, offs, len(self.spec.level_off) - 1,
+        call("mvp_det_nms", ptr(cand), n, self.n_priors, offs, len(self.spec.level_off) - 1,
              int(self.cfg["nms_pre"]), ctypes.c_float(self.cfg["score_thr"]), ctypes.c_float(self.cfg["iou_threshold"]),
-             cap, ctypes.c_float(fx), ctypes.c_float(fy), ctypes.c_void_p(dets.data_ptr()),
-             ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream(cand.device).cuda_stream))
+             cap, ctypes.c_float(fx), ctypes.c_float(fy), ptr(dets), ptr(counts), stream(cand.device))
         return dets, counts
 
     def nms(self, det: dict):
