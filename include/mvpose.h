@@ -975,10 +975,9 @@ int mvp_bundle_adjust(const float* kpts_dev, int64_t n_points, int V, const doub
  *   allocation, no host synchronisation.  Time, one MI355X, T = 100 000, P = 17, two views, chunk 0:
  *   3.71 ms against 2.23 ms for one trial of mvp_trajectory_fit, 1.67x.
  * Out of scope: blocks of Σ further than lag 1, the uncertainty of λ itself, and a covariance for
- * mvp_skeleton_fit (its chains are coupled: the per-chain inverse is not its posterior); sub-frame
- * time offsets between the cameras (mvp_epipolar_lag_cost finds whole frames);
+ * mvp_skeleton_fit (its chains are coupled: the per-chain inverse is not its posterior);
  * coupling between chains such as bone lengths (chains stay independent here; mvp_skeleton_fit
- * below couples them).
+ * below couples them).  Sub-frame time offsets between the cameras: mvp_trajectory_fit_lag below.
  * ------------------------------------------------------------------------- */
 int mvp_trajectory_fit_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
 int mvp_trajectory_fit_system(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
@@ -998,6 +997,80 @@ int mvp_trajectory_fit_cov(const float* kpts_dev, int T, int P, int V, const dou
                            int weights, const double* gauss_dev, float min_conf, float cov_floor, double huber_delta,
                            double lambda_smooth, int chunk, void* workspace_dev, int64_t workspace_bytes,
                            float* out_cov_dev, float* out_cross_dev, uint8_t* out_status_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The trajectory fit with sub-frame time offsets between the cameras.  No reference counterpart: the
+ * reference aligns its recordings to a whole frame by hand.  Free-running cameras are never closer
+ * than a fraction of a frame; a wrist at 3-5 m/s moves 10-17 cm per frame at 30 fps, and a solver
+ * that takes the views of frame t for one instant puts that into the 3D point as a bias.
+ *
+ * Time: frame t of view i was taken at rig instant t + s_i (mvp_epipolar_lag_cost's convention).
+ * The caller splits s_i = n_i + a_i, n_i = floor(s_i), 0 <= a_i < 1, aligns the recordings by the
+ * integers n_i, and passes frac_host [n_cam_idx] float64, a_i of the listed view i.  Each a_i has
+ * to be finite with 0 <= a_i < 1.
+ *   Unknowns: X_t, chain p's position at the integer rig instants t = 0..T-1.  Chains are independent.
+ *   Observation: view i's frame t scores the point
+ *       Y = (1 - a_i)·X_t + a_i·X_{t+1}     (Y = X_t itself when a_i = 0: X_{t+1} is not read)
+ *     with r = pi_i(Y) - z_i.  Used view, observation, weight, mask, rho, omega and the forward
+ *     model are mvp_trajectory_fit's, with one rule added: a view with a_i > 0 is not used in frame
+ *     T-1, whose neighbour does not exist.  nviews(t, p) counts accordingly.
+ *   Cost per chain: f(X) = Σ_t Σ_used rho + ½ λ Σ_{t=2}^{T-1} |X_t - 2 X_{t-1} + X_{t-2}|², and +inf
+ *     when a used view has P_z <= 0 at its Y.
+ *   Linearisation: with H_i = Jᵀ W~ J and g_i = Jᵀ W~ r, J = d pi_i / dY, all at Y, the used
+ *     observation (t, i) gives node t (1-a_i)²·H_i and (1-a_i)·g_i, node t+1 a_i²·H_i and a_i·g_i,
+ *     and the pair (t, t+1) the symmetric block C_t += a_i(1-a_i)·H_i (a view with a_i = 0 adds
+ *     exact zeros to node t+1 and to C_t, whatever its H_i is).  With H~_t, g~_t the nodes'
+ *     sums,
+ *       A = blockdiag(H~) + offdiag(C) + λ·(D₂ᵀD₂ ⊗ I₃),    G = g~ + λ·(D₂ᵀD₂ ⊗ I₃)·X,
+ *     offdiag(C) holding C_t in the blocks (t, t+1) and (t+1, t).  The Marquardt factor multiplies
+ *     the diagonal entries of A only.
+ *   Valid chain, the Levenberg-Marquardt loop, the status byte, the stop tests and chunk: word for
+ *     word mvp_trajectory_fit's, with P_z tested at the Ys of the seed.  A seed frame that is not
+ *     finite makes its chain invalid as there.
+ *   Offset derivative: per chain p and listed view i, over the used (t, i) with t + 1 < T (a view
+ *     with a_i = 0 included; its frame T-1 excluded), with d = J·(X_{t+1} - X_t) at Y:
+ *       ga[p][i] = Σ_t dᵀ W~ r,      ha[p][i] = Σ_t dᵀ W~ d.
+ *     ga is the derivative of the chain's cost with respect to a_i at fixed X, and so, at a fitted
+ *     state, the total derivative of the minimised cost (the envelope theorem): offsets can be
+ *     refined from fits alone.  ha is the Gauss-Newton curvature at fixed X; the minimised cost's
+ *     is much smaller (the trajectory gives way), so a Newton step needs differences of ga between
+ *     fits, not ha.
+ * fp64 on the device, FMA contraction allowed, no floating-point atomics, fixed summation orders
+ * (a lane gathers its own node's terms; costs, ga and ha per tile of 256 frames in a fixed order,
+ * the tiles ascending): the same inputs give the same bits on every call.  With every a_i = 0 the
+ * call states mvp_trajectory_fit's problem; its sums are formed in another order, so the results
+ * agree to fp64 rounding, not bit for bit.
+ *
+ * mvp_trajectory_fit_lag_plan : as mvp_trajectory_fit_plan, for the workspace of mvp_trajectory_fit_lag.
+ * mvp_trajectory_fit_lag_system : ONE linearisation at the float32 trajectory xyz_dev [T][P][3]; no
+ *   solve, no state, no validity test.  out_H_dev [T][P][6] (H~_t), out_C_dev [T][P][6] (C_t, the
+ *   block between t and t+1, (xx, xy, xz, yy, yz, zz); row T-1 is zero), out_g_dev [T][P][3] (g~_t),
+ *   out_nviews_dev [T][P] uint8, out_cost_dev [P][2] float64 as mvp_trajectory_fit_system's,
+ *   out_dlag_dev [P][n_cam_idx][2] float64: {ga, ha}.  All six are required.
+ * mvp_trajectory_fit_lag : the whole fit from the seed xyz0_dev, stream-ordered, with no host
+ *   synchronisation, no allocation and no decision on the host.  Outputs as mvp_trajectory_fit's
+ *   (out_resid: Σ_used s² of frame t's observations at their Y), and out_dlag_dev
+ *   [P][n_cam_idx][2] float64 or NULL: {ga, ha} at the final state, NaN for an invalid chain.
+ * Requires what mvp_trajectory_fit requires, and frac_host as above: frac_host NULL, or an entry
+ * that is not finite, < 0 or >= 1, returns MVP_ERR_ARG naming frac before any device work.
+ * Out of scope: a covariance for this fit, bone coupling with offsets, offsets that drift over a
+ * recording, offsets in mvp_triangulate* and mvp_bundle_adjust, interpolation of a higher order
+ * than linear (on a strongly curved path the linear model biases the offsets: DESIGN.md §4.17).
+ * ------------------------------------------------------------------------- */
+int mvp_trajectory_fit_lag_plan(int T, int P, int chunk, int* chunk_used, int* n_chunks, int64_t* workspace_bytes);
+int mvp_trajectory_fit_lag_system(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                                  const int* cam_idx_host, int n_cam_idx, const double* frac_host,
+                                  const float* xyz_dev, const uint8_t* mask_dev, int weights, const double* gauss_dev,
+                                  float min_conf, float cov_floor, double huber_delta, double* out_H_dev,
+                                  double* out_C_dev, double* out_g_dev, uint8_t* out_nviews_dev, double* out_cost_dev,
+                                  double* out_dlag_dev, void* stream);
+int mvp_trajectory_fit_lag(const float* kpts_dev, int T, int P, int V, const double* cams_dev, int n_cams,
+                           const int* cam_idx_host, int n_cam_idx, const double* frac_host, const float* xyz0_dev,
+                           const uint8_t* mask_dev, int weights, const double* gauss_dev, float min_conf,
+                           float cov_floor, double huber_delta, double lambda_smooth, int max_iter, double tol,
+                           int chunk, void* workspace_dev, int64_t workspace_bytes, float* out_xyz_dev,
+                           float* out_resid_dev, uint8_t* out_nviews_dev, double* out_cost_dev, uint8_t* out_status_dev,
+                           double* out_dlag_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The trajectory fit with a person's joints coupled by bone lengths: the third of the costs the

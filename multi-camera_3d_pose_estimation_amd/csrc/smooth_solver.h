@@ -19,6 +19,13 @@
 // the diagonal and lag-1 blocks of A⁻¹.  Such a source needs failed(p) and none of the backsub
 // members.
 //
+// A source that sets kHasCross = true has a symmetric 3x3 data block between neighbouring frames
+// as well (the trajectory fit with sub-frame camera offsets): cross(raw, C) gives the block between
+// the frame before raw's and raw's own, zero for frame 0.  It belongs to the lane that owns the
+// later frame of the pair, as a second-difference row belongs to the lane that owns its last frame,
+// so every pair enters exactly one window, whether it lies inside a chunk, inside a separator or
+// across the edge of one.  The other sources compile to what they were.
+//
 // The three kernels of a source are solve_eliminate_kernel<A>, solve_reduce_kernel<A> and
 // solve_backsub_kernel<A> (below the per-lane code); bind_core fills a source's SolveCore fields
 // from the plan.  The per-lane functions also compile for the host, where a CPU build can step
@@ -72,6 +79,12 @@ template <class A, class = void>
 struct keeps_pivot : std::false_type {};
 template <class A>
 struct keeps_pivot<A, std::enable_if_t<A::kKeepPivot>> : std::true_type {};
+
+// A::kHasCross, likewise.
+template <class A, class = void>
+struct has_cross : std::false_type {};
+template <class A>
+struct has_cross<A, std::enable_if_t<A::kHasCross>> : std::true_type {};
 
 MVP_SMOOTH_HD constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }  // i >= j
 MVP_SMOOTH_HD constexpr int sym(int i, int j) { return i >= j ? tri(i, j) : tri(j, i); }
@@ -176,6 +189,17 @@ MVP_SMOOTH_HD void add_element(double (&M)[120], double lam, D damp) {
                 M[tri(3 * (B + i) + d, 3 * (B + j) + d)] += i == j ? damped(lam * v[i] * v[j], damp) : lam * v[i] * v[j];
 }
 
+// The symmetric 3x3 data block C = (xx, xy, xz, yy, yz, zz) between window blocks B-1 and B (rows:
+// the later frame).  Off the diagonal: no Marquardt factor.
+template <int B>
+MVP_SMOOTH_HD void add_cross(double (&M)[120], const double (&C)[6]) {
+    constexpr int o = 3 * B;
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+#pragma unroll
+        for (int e = 0; e < 3; e++) M[tri(o + d, o - 3 + e)] += C[d >= e ? sym3(d, e) : sym3(e, d)];
+}
+
 // The frames lane (chain p, chunk k) works on.
 struct LaneRange {
     int p, k;
@@ -221,6 +245,18 @@ MVP_SMOOTH_HD void eliminate_lane(const A& a, int64_t lane) {
         cnt += a.frame_weight(fb, W, z);
         add_data<3, A::kInfoForm>(M, r, W, z, damp);
     }
+    if constexpr (has_cross<A>::value) {
+        // the pairs that end in frames a and b: (left separator, a) and (a, b)
+        double X[6];
+        if (R.k > 0) {
+            a.cross(fa, X);
+            add_cross<2>(M, X);
+        }
+        if (has_b) {
+            a.cross(fb, X);
+            add_cross<3>(M, X);
+        }
+    }
     if (R.k > 0) {
         add_element<0>(M, a.lambda, damp);
         if (has_b) add_element<1>(M, a.lambda, damp);
@@ -237,6 +273,11 @@ MVP_SMOOTH_HD void eliminate_lane(const A& a, int64_t lane) {
             cnt += a.frame_weight(fc, W, z);
             add_data<4, A::kInfoForm>(M, r, W, z, damp);
             add_element<2>(M, a.lambda, damp);
+            if constexpr (has_cross<A>::value) {
+                double X[6];
+                a.cross(fc, X);
+                add_cross<4>(M, X);
+            }
         }
         // frame a leaves: pivot P = M[a][a]
         const double s[6] = {M[tri(6, 6)], M[tri(7, 6)], M[tri(8, 6)], M[tri(7, 7)], M[tri(8, 7)], M[tri(8, 8)]};

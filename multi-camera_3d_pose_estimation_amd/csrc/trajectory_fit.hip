@@ -8,7 +8,7 @@
 // rank-2 block, frames seen by none with nothing, and the prior carries them.  Stream-ordered
 // launches, arithmetic in fp64, FMA contraction on (no bit contract), no floating-point atomics.
 // The kernels are trajectory_fit_kernels.h's with no coupling between chains (NoCoupling) and
-// smooth_solver.h's over trajectory_fit_solver.h's frame source; only decide is this file's own:
+// smooth_solver.h's over trajectory_fit_solver.h's frame source:
 //
 //   fit_prepare_kernel<2>   one lane per (t, p): the f64 copy of the seed, the number of used views,
 //              and the two numbers a chain's validity is summed from (frames with >= 2 used views;
@@ -22,7 +22,8 @@
 //   fit_sum_kernel<2>   per chain, the frames' two numbers in tiles of 256 frames: each of a
 //              workgroup's 4 rows of lanes adds its frames in ascending order, the rows are added
 //              in order.
-//   fit_decide_kernel   one lane per chain: the tiles' sums in ascending order (the same inputs give
+//   fit_decide_kernel   (trajectory_fit_decide.h, shared with the fit with camera offsets) one lane
+//              per chain: the tiles' sums in ascending order (the same inputs give
 //              the same bits), then mode 0: validity; mode 1: the seed's cost; mode 2: accept /
 //              reject, mu, the stop tests, and which of the two state buffers holds the state (the
 //              rules themselves are trajectory_fit_kernels.h's, shared with the skeleton fit).
@@ -44,45 +45,7 @@
 // it, and the covariance sweep of smooth_solver.h.
 //
 // Register / LDS / scratch figures and the measurements are in DESIGN.md §4.14 and §4.16.
-#include "trajectory_fit_kernels.h"
-
-namespace {
-
-// mode 0: validity from prepare's sums; mode 1: the seed's cost; mode 2: the trial's.
-__global__ __launch_bounds__(kSmBlock) void fit_decide_kernel(FitChain ch, const double* __restrict__ part, int n_tiles,
-                                                              int P, int mode, int max_iter, double tol,
-                                                              int* __restrict__ bad) {
-    const int p = blockIdx.x * kSmBlock + threadIdx.x;
-    if (p >= P) return;
-    if (mode != 0 && ch.done[p]) return;
-    double s[2];
-    fit_sum_tiles(part, n_tiles, P, p, s);
-    bad[p] = 0;
-    if (mode == 0) {
-        fit_chain_reset(ch, p, fit_chain_valid(s[0], s[1]), 0x40);
-        return;
-    }
-    const double ft = s[0] + s[1];
-    if (mode == 1) {
-        const bool fin = fit_seed_ok(ft);
-        ch.f[p] = ch.fseed[p] = fin ? ft : __builtin_nan("");
-        ch.done[p] = (fin && max_iter > 0) ? 0 : 1;
-        ch.status[p] = fin ? 0x40 : 0x80;
-        ch.relin[p] = 0;   // the seed has just been linearised
-        return;
-    }
-    const LmStep st = lm_step(ch.f[p], ft, ch.rej[p] != 0, ch.mu[p], ch.status[p], max_iter, tol);
-    if (st.accept) {
-        ch.cur[p] ^= 1;
-        ch.f[p] = ft;
-    }
-    ch.mu[p] = st.mu;
-    ch.relin[p] = st.accept ? 1 : 0;
-    ch.status[p] = st.status;
-    ch.done[p] = st.done ? 1 : 0;
-}
-
-}  // namespace
+#include "trajectory_fit_decide.h"
 
 // ------------------------------------------------------------------------------- host side
 

@@ -383,21 +383,44 @@ void fit_launch_sum(hipStream_t s, const FitPlan& pl, const double* cost, int T,
     hipLaunchKernelGGL(fit_sum_kernel<NC>, dim3((unsigned)pl.sum_blocks), dim3(kFitRows * 64), 0, s, cost, T, P, done, part);
 }
 
+// The kernels fit_run launches for the data term and the solve: these over the coupling policy C.
+// mvp_trajectory_fit_lag has its own set (trajectory_fit_lag.hip).
+//   Solve, kCosts                 the solver's frame source and the cost terms a frame has
+//   bind(sa, ws)                  what the source has beyond FitSolveArgs' fields
+//   prepare(...), terms<JAC>(...) the launches
+template <class C>
+struct FitLaunch {
+    using Solve = FitSolveArgs;
+    static constexpr int kCosts = C::kCosts;
+    C cp;
+    void bind(Solve&, char*) const {}
+    void prepare(dim3 grid, dim3 blk, hipStream_t s, const FitTerms& ta, const float* xyz0) const {
+        hipLaunchKernelGGL(fit_prepare_kernel<kCosts>, grid, blk, 0, s, ta.o, xyz0, const_cast<double*>(ta.x64), ta.cost);
+    }
+    template <bool JAC>
+    void terms(dim3 grid, dim3 blk, hipStream_t s, const FitTerms& ta) const {
+        hipLaunchKernelGGL((fit_terms_kernel<JAC, C>), grid, blk, 0, s, ta, cp);
+    }
+};
+
 // The launch sequence of a fit: prepare, sum, decide(0), terms<JAC>, sum, decide(1), then max_iter
 // x (eliminate, reduce, backsub, terms at the trial, sum, decide(2), terms<JAC> at the state) and
-// output, over the workspace ws of plan pl.  decide(mode, ch, part, bad) launches the caller's decide
-// kernel and output(grid, block, ch, x64) its output kernel.
-template <class C, class Decide, class Output>
-void fit_run(const char* fn, hipStream_t s, const FitPlan& pl, char* ws, const FitObs& o, const C& cp,
-             double lambda_smooth, const float* xyz0, int max_iter, Decide decide, Output output) {
+// output, over the workspace ws of plan pl, with the kernels of K (a FitLaunch, or what has its
+// members).  decide(mode, ch, part, bad) launches the caller's decide kernel and
+// output(grid, block, ch, x64) its output kernel.
+template <class K, class Decide, class Output>
+void fit_run_with(const char* fn, hipStream_t s, const FitPlan& pl, char* ws, const FitObs& o, const K& k,
+                  double lambda_smooth, const float* xyz0, int max_iter, Decide decide, Output output) {
+    using Solve = typename K::Solve;
     const int T = o.T, P = o.P;
     double* part = reinterpret_cast<double*>(ws + pl.off_part);
-    FitSolveArgs sa{};
+    Solve sa{};
     bind_core(sa, ws, pl.sp, T, P, lambda_smooth);
     sa.H = reinterpret_cast<double*>(ws + pl.off_H);
     sa.g = reinterpret_cast<double*>(ws + pl.off_g);
     sa.x64 = reinterpret_cast<double*>(ws + pl.off_x);
     sa.ch = bind_chain(ws + pl.off_chain, P);
+    k.bind(sa, ws);
     FitTerms ta{};
     ta.o = o;
     ta.x64 = sa.x64;
@@ -409,32 +432,38 @@ void fit_run(const char* fn, hipStream_t s, const FitPlan& pl, char* ws, const F
     const dim3 flat(tri_grid(fn, (int64_t)T * P)), blk(kBlock);
     const dim3 chain_grid((unsigned)((P + kSmBlock - 1) / kSmBlock)), lane_grid((unsigned)pl.sp.n_blocks), sm_blk(kSmBlock);
     auto sum_decide = [&](int mode) {
-        fit_launch_sum<C::kCosts>(s, pl, ta.cost, T, P, mode == 0 ? (const int*)nullptr : sa.ch.done, part);
+        fit_launch_sum<K::kCosts>(s, pl, ta.cost, T, P, mode == 0 ? (const int*)nullptr : sa.ch.done, part);
         decide(mode, sa.ch, part, sa.bad);
         MVP_HIP(hipGetLastError());
     };
     MVP_HIP(hipMemsetAsync(sa.cnt, 0, (size_t)P * 8, s));
-    hipLaunchKernelGGL(fit_prepare_kernel<C::kCosts>, flat, blk, 0, s, ta.o, xyz0, sa.x64, ta.cost);
+    k.prepare(flat, blk, s, ta, xyz0);
     MVP_HIP(hipGetLastError());
     sum_decide(0);
     ta.trial = 0;
-    hipLaunchKernelGGL((fit_terms_kernel<true, C>), flat, blk, 0, s, ta, cp);
+    k.template terms<true>(flat, blk, s, ta);
     sum_decide(1);
     for (int it = 0; it < max_iter; it++) {
-        hipLaunchKernelGGL(solve_eliminate_kernel<FitSolveArgs>, lane_grid, sm_blk, 0, s, sa);
-        hipLaunchKernelGGL(solve_reduce_kernel<FitSolveArgs>, chain_grid, sm_blk, 0, s, sa);
-        hipLaunchKernelGGL(solve_backsub_kernel<FitSolveArgs>, lane_grid, sm_blk, 0, s, sa);
+        hipLaunchKernelGGL(solve_eliminate_kernel<Solve>, lane_grid, sm_blk, 0, s, sa);
+        hipLaunchKernelGGL(solve_reduce_kernel<Solve>, chain_grid, sm_blk, 0, s, sa);
+        hipLaunchKernelGGL(solve_backsub_kernel<Solve>, lane_grid, sm_blk, 0, s, sa);
         ta.trial = 1;
-        hipLaunchKernelGGL((fit_terms_kernel<false, C>), flat, blk, 0, s, ta, cp);
+        k.template terms<false>(flat, blk, s, ta);
         sum_decide(2);
         if (it + 1 < max_iter) {
             ta.trial = 0;
-            hipLaunchKernelGGL((fit_terms_kernel<true, C>), flat, blk, 0, s, ta, cp);
+            k.template terms<true>(flat, blk, s, ta);
             MVP_HIP(hipGetLastError());
         }
     }
     output(flat, blk, sa.ch, sa.x64);
     MVP_HIP(hipGetLastError());
+}
+
+template <class C, class Decide, class Output>
+void fit_run(const char* fn, hipStream_t s, const FitPlan& pl, char* ws, const FitObs& o, const C& cp,
+             double lambda_smooth, const float* xyz0, int max_iter, Decide decide, Output output) {
+    fit_run_with(fn, s, pl, ws, o, FitLaunch<C>{cp}, lambda_smooth, xyz0, max_iter, decide, output);
 }
 
 }  // namespace

@@ -77,6 +77,40 @@ struct FitSolveArgs : SolveCore {
     }
 };
 
+// The frames of mvp_trajectory_fit_lag: the same buffers, and the data block between frames t and
+// t+1 in Cx [T][P][6] (row T-1 zero).  A frame's record carries the block that ends in it.
+struct FitLagRaw {
+    double h[6], b[3], c[6];
+};
+
+struct FitLagSolveArgs : FitSolveArgs {
+    const double* Cx;   // [T][P][6]
+    using Raw = FitLagRaw;
+    static constexpr bool kHasCross = true;
+    MVP_SMOOTH_HD FitLagRaw load_raw(int t, int p) const {
+        const int64_t e = (int64_t)t * P + p;
+        FitLagRaw f;
+#pragma unroll
+        for (int k = 0; k < 6; k++) f.h[k] = H[6 * e + k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) f.b[k] = g[3 * e + k];
+#pragma unroll
+        for (int k = 0; k < 6; k++) f.c[k] = t > 0 ? Cx[6 * (e - P) + k] : 0.0;
+        return f;
+    }
+    MVP_SMOOTH_HD bool frame_weight(const FitLagRaw& f, double (&W)[6], double (&z)[3]) const {
+#pragma unroll
+        for (int k = 0; k < 6; k++) W[k] = f.h[k];
+#pragma unroll
+        for (int k = 0; k < 3; k++) z[k] = f.b[k];
+        return false;
+    }
+    MVP_SMOOTH_HD void cross(const FitLagRaw& f, double (&C)[6]) const {
+#pragma unroll
+        for (int k = 0; k < 6; k++) C[k] = f.c[k];
+    }
+};
+
 // The frames of mvp_trajectory_fit_cov: the same information-form buffer at a given state, no
 // Marquardt factor, the inverse pivots kept; reduce_cov_chain and cov_lane then give Σ = A⁻¹.
 struct FitCovArgs : SolveCore, CovCore {
@@ -151,6 +185,25 @@ inline FitPlan fit_plan(const char* fn, int T, int P, int chunk, int n_costs = 2
     b = align256(b + (int64_t)pl.n_tiles * P * n_costs * 8);
     pl.bytes = b;
     return pl;
+}
+
+// What mvp_trajectory_fit_lag adds behind the fit's workspace: the blocks between neighbouring
+// frames and the tiles' sums of the offset derivative, [tile][P][kLagViews][2].
+constexpr int kLagViews = 8;   // the most views a call lists (tri_common.h's kMaxCams)
+
+struct LagPlan {
+    int64_t off_C, off_dpart, bytes;
+};
+
+inline LagPlan lag_plan(const FitPlan& pl, int T, int P) {
+    LagPlan lp;
+    int64_t b = pl.bytes;
+    lp.off_C = b;
+    b = align256(b + (int64_t)T * P * 6 * 8);
+    lp.off_dpart = b;
+    b = align256(b + (int64_t)pl.n_tiles * P * kLagViews * 2 * 8);
+    lp.bytes = b;
+    return lp;
 }
 
 // The chains' state in the plan's chain block c.

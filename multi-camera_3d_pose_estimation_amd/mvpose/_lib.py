@@ -143,6 +143,15 @@ SIGNATURES = {
     "mvp_trajectory_fit_cov": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p,
                                        c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_double, c_int,
                                        c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_trajectory_fit_lag_plan": (c_int, [c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
+    "mvp_trajectory_fit_lag_system": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int,
+                                              P(c_double), c_void_p, c_void_p, c_int, c_void_p, c_float, c_float,
+                                              c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "mvp_trajectory_fit_lag": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, P(c_double),
+                                       c_void_p, c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_double, c_int,
+                                       c_double, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
     "mvp_skeleton_fit_plan": (c_int, [c_int, c_int, c_int, c_int, P(c_int), P(c_int), P(c_int64)]),
     "mvp_skeleton_fit_system": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p,
                                         c_void_p, c_int, c_void_p, c_float, c_float, c_double, c_int, P(c_int), c_int,

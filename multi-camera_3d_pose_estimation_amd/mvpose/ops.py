@@ -654,6 +654,80 @@ def trajectory_fit_cov(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     return out, cross, status
 
 
+def trajectory_fit_lag_plan(T: int, P: int, chunk: int = 0):
+    """What trajectory_fit_lag will use for (T, P, chunk) (mvp_trajectory_fit_lag_plan): the chunk
+    length, the chunks per chain and the workspace bytes."""
+    return _plan3("mvp_trajectory_fit_lag_plan", T, P, chunk)
+
+
+def _lag_args(args, frac, nv):
+    """The fits' leading arguments with frac_host behind n_cam_idx: frac (nv,) fractional offsets,
+    each in [0, 1) (the library checks the values)."""
+    a = np.asarray(frac, dtype=np.float64).reshape(-1)
+    if a.size != nv:
+        raise ValueError(f"frac must hold one offset per listed view ({nv}), got {a.size}")
+    return args[:8] + ((ctypes.c_double * nv)(*a.tolist()),) + args[8:]
+
+
+def trajectory_fit_lag_system(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], frac,
+                              xyz: torch.Tensor, *, weights: str = "conf", gauss: torch.Tensor | None = None,
+                              mask: torch.Tensor | None = None, min_conf: float = 0.0, cov_floor: float = 1.0,
+                              huber_delta: float = 0.0):
+    """One linearisation of the trajectory fit with sub-frame camera offsets
+    (mvp_trajectory_fit_lag_system; stated in include/mvpose.h) at the float32 trajectory xyz
+    (T, P, 3): view i's frame t scores (1 − frac[i])·X_t + frac[i]·X_{t+1}.
+
+    frac (NV,) host floats in [0, 1), one per entry of cam_idx; the other arguments as for
+    trajectory_fit_system.  Returns (H (T, P, 6) float64: the nodes' blocks; C (T, P, 6) float64: the
+    block between t and t+1, zero in the last row; g (T, P, 3) float64; nviews (T, P) uint8;
+    cost (P, 2) float64; dlag (P, NV, 2) float64: the cost's first derivative with respect to
+    frac[i] at fixed xyz and its Gauss-Newton curvature), all on the GPU."""
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz, weights, gauss, mask, min_conf, cov_floor, huber_delta)
+    nv = len(cam_idx)
+    args = _lag_args(args, frac, nv)
+    dev = kpts.device
+    H = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
+    C = torch.empty((T, P, 6), dtype=torch.float64, device=dev)
+    g = torch.empty((T, P, 3), dtype=torch.float64, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    dlag = torch.empty((P, nv, 2), dtype=torch.float64, device=dev)
+    call("mvp_trajectory_fit_lag_system", *args, ptr(H), ptr(C), ptr(g), ptr(nviews), ptr(cost), ptr(dlag), stream(dev))
+    return H, C, g, nviews, cost, dlag
+
+
+def trajectory_fit_lag(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], frac, xyz0: torch.Tensor, *,
+                       weights: str = "conf", gauss: torch.Tensor | None = None, mask: torch.Tensor | None = None,
+                       min_conf: float = 0.0, cov_floor: float = 1.0, huber_delta: float = 0.0,
+                       lambda_smooth: float = 1.0, max_iter: int = 30, tol: float = 1e-6, chunk: int = 0):
+    """trajectory_fit for cameras that are a fraction of a frame apart (mvp_trajectory_fit_lag;
+    stated in include/mvpose.h): frame t of view i was taken frac[i] of a frame after rig instant t
+    and scores the chain's position interpolated between X_t and X_{t+1}; a view with frac > 0 is
+    not used in the last frame.  frac (NV,) host floats in [0, 1); the recordings are aligned by
+    the whole frames beforehand (sync.split_frame_offsets, sync.apply_frame_offsets).  The other
+    arguments, the solver and the outputs as for trajectory_fit.  Stream-ordered, no host
+    synchronisation.
+
+    Returns (xyz, resid, nviews, cost, status as trajectory_fit's; dlag (P, NV, 2) float64: per
+    chain and view the derivative of the minimised cost with respect to frac[i] and the
+    Gauss-Newton curvature at fixed xyz, NaN for an invalid chain), all on the GPU."""
+    T, P, args, _bits = _fit_args(kpts, cams, cam_idx, xyz0, weights, gauss, mask, min_conf, cov_floor, huber_delta)
+    nv = len(cam_idx)
+    args = _lag_args(args, frac, nv)
+    _, _, nbytes = trajectory_fit_lag_plan(T, P, chunk)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((T, P, 3), dtype=torch.float32, device=dev)
+    resid = torch.empty((T, P), dtype=torch.float32, device=dev)
+    nviews = torch.empty((T, P), dtype=torch.uint8, device=dev)
+    cost = torch.empty((P, 2), dtype=torch.float64, device=dev)
+    status = torch.empty((P,), dtype=torch.uint8, device=dev)
+    dlag = torch.empty((P, nv, 2), dtype=torch.float64, device=dev)
+    call("mvp_trajectory_fit_lag", *args, float(lambda_smooth), int(max_iter), float(tol), int(chunk), ptr(work),
+         int(nbytes), ptr(out), ptr(resid), ptr(nviews), ptr(cost), ptr(status), ptr(dlag), stream(dev))
+    return out, resid, nviews, cost, status, dlag
+
+
 def skeleton_fit_plan(T: int, P: int, J: int, chunk: int = 0):
     """What skeleton_fit will use for (T, P, J, chunk) (mvp_skeleton_fit_plan): the chunk length of
     its time-parallel solve, the chunks per chain and the workspace bytes."""

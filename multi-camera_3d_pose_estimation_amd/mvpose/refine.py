@@ -368,7 +368,7 @@ def _fit_inputs(kpts_2d, camera_params, seed, camera_indices, weights, gauss, ma
 
 def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="conf", gauss=None, mask=None,
                    lambda_smooth=1.0, huber_px=0.0, min_conf=0.0, cov_floor=1.0, max_iter=30, tol=1e-6, chunk=0,
-                   return_info=False, device=None, with_cov=False):
+                   return_info=False, device=None, with_cov=False, frame_offsets=None):
     """Trajectories fitted to the 2D keypoints, so that a frame seen by a single camera still counts
     (mvp_trajectory_fit, stated in include/mvpose.h; no reference counterpart: the reference's
     sgd_optimize scores the same pixels, in f32 with Adam, with no mask, no robust loss and no
@@ -402,14 +402,32 @@ def fit_trajectory(kpts_2d, camera_params, seed, camera_indices=None, weights="c
     (mvp_trajectory_fit_cov): "cov" (T, [Np,] J, 3, 3) float32, Σ_{t,t} in world units², and
     "cov_next", same shape, Σ_{t,t+1} (row: coordinate of X_t; NaN in the last frame); all NaN for a
     joint that is returned as it came.  Over a stretch seen by one camera its large axis lies along
-    that camera's rays: it says which frames wander, and in which direction."""
+    that camera's rays: it says which frames wander, and in which direction.
+
+    frame_offsets (NV,) floats in [0, 1), one per used view: cameras that are a fraction of a frame
+    apart (mvp_trajectory_fit_lag).  Frame t of view i was taken frame_offsets[i] of a frame after
+    rig instant t and scores the trajectory interpolated between frames t and t+1; the result is
+    the trajectory at the rig instants.  Align the recordings by the whole frames first:
+    sync.estimate_frame_offsets -> info["s"] -> sync.split_frame_offsets -> (n, a);
+    sync.apply_frame_offsets(arrays, n, axes); then frame_offsets=a (sync.refine_frame_offsets
+    sharpens s beforehand).  A view with an offset > 0 is not used in the last frame.  info gains
+    "dlag" ([Np,] J, NV, 2) float64: per joint and view the derivative of the minimised cost with
+    respect to that view's offset, and the curvature at fixed trajectory; NaN for a joint returned
+    as it came.  with_cov is not available with offsets.  None takes the path without offsets."""
+    if frame_offsets is not None and with_cov:
+        raise ValueError("with_cov is not available with frame_offsets")
     k, x0, idx, cams, g, m, lead, finish = _fit_inputs(kpts_2d, camera_params, seed, camera_indices, weights, gauss, mask,
                                                        device)
-    out, resid, nviews, cost, status = ops.trajectory_fit(
-        k, cams, idx, x0, weights=weights, gauss=g, mask=m, min_conf=min_conf, cov_floor=cov_floor,
-        huber_delta=huber_px, lambda_smooth=lambda_smooth, max_iter=max_iter, tol=tol, chunk=chunk)
+    kw = dict(weights=weights, gauss=g, mask=m, min_conf=min_conf, cov_floor=cov_floor, huber_delta=huber_px,
+              lambda_smooth=lambda_smooth, max_iter=max_iter, tol=tol, chunk=chunk)
+    if frame_offsets is None:
+        out, resid, nviews, cost, status = ops.trajectory_fit(k, cams, idx, x0, **kw)
+    else:
+        out, resid, nviews, cost, status, dlag = ops.trajectory_fit_lag(k, cams, idx, frame_offsets, x0, **kw)
     info = {"resid": resid.reshape(lead), "nviews": nviews.reshape(lead), "cost": cost.reshape(lead[1:] + (2,)),
             "status": status.reshape(lead[1:])}
+    if frame_offsets is not None:
+        info["dlag"] = dlag.reshape(lead[1:] + (len(idx), 2))
     if with_cov and return_info:
         c, cn, _ = ops.trajectory_fit_cov(k, cams, idx, out, weights=weights, gauss=g, mask=m, min_conf=min_conf,
                                           cov_floor=cov_floor, huber_delta=huber_px, lambda_smooth=lambda_smooth,

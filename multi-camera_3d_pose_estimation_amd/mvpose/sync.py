@@ -9,6 +9,15 @@ instant when ``l = s_a - s_b``.
   problem is stated in include/mvpose.h), then ``offsets_from_curves``: per pair the lag of the
   lowest mean cost with a rejection rule, and a least-squares fit of ``s`` over the accepted pairs.
 * ``apply_frame_offsets``: cuts every camera to the instants all cameras saw (pure indexing).
+* ``split_frame_offsets``: ``s = n + a``, the whole frames to align by and the fractions that
+  ``refine.fit_trajectory(frame_offsets=a)`` models.
+* ``refine_frame_offsets``: refines ``s`` to a fraction of a frame from trajectory fits alone.
+
+Synchronise, then fit: ``_, info = estimate_frame_offsets(kpts_2d, params)``; ``n, a =
+split_frame_offsets(info["s"])``; ``(kpts,), _ = apply_frame_offsets([kpts_2d], n, [3])``; a seed
+at those instants (e.g. triangulate and smooth the aligned keypoints); optionally ``s, _ =
+refine_frame_offsets(kpts_2d, params, seed_at_camera_0_frames, info["s"])``; then
+``refine.fit_trajectory(kpts, params, seed, frame_offsets=a)``.
 """
 from __future__ import annotations
 
@@ -155,7 +164,8 @@ def apply_frame_offsets(arrays, offsets_int, view_axes):
     arrays: arrays with time on axis 0 and the cameras on axis view_axes[i] (kpts_2d (T, J, 3, V):
     3; heatmaps_2d (T, V, J, 6): 1); a None entry stays None.  Returns (aligned arrays, each of
     T - (max s - min s) frames, first (V,) int64: the index of each camera's first kept frame).
-    Pure indexing: sub-frame resampling is out of scope."""
+    Pure indexing: the fractions of a frame that remain (split_frame_offsets) are not resampled
+    away but modelled by refine.fit_trajectory(frame_offsets=a)."""
     s = np.asarray(offsets_int, np.int64)
     if s.ndim != 1 or (s == NO_OFFSET).any():
         raise ValueError(f"offsets_int must be (V,) with every camera's offset known, got {s}")
@@ -180,3 +190,85 @@ def apply_frame_offsets(arrays, offsets_int, view_axes):
             res[tuple(sel)] = arr[tuple(src)]
         out.append(res)
     return out, first
+
+
+def split_frame_offsets(s):
+    """s (V,) fractional offsets (estimate_frame_offsets' info["s"]; s[0] = 0 is the gauge) ->
+    (n (V,) int64 = floor(s), a (V,) float64 = s - n in [0, 1)): align the recordings by n
+    (apply_frame_offsets), hand a to refine.fit_trajectory(frame_offsets=a)."""
+    s = np.asarray(s, np.float64)
+    if s.ndim != 1 or not np.isfinite(s).all():
+        raise ValueError(f"s must be (V,) with every camera's offset known, got {s}")
+    n = np.floor(s)
+    a = s - n
+    up = a >= 1.0                      # s a hair below an integer: s - floor(s) rounds to 1
+    n, a = np.where(up, n + 1, n), np.where(up, 0.0, a)
+    return n.astype(np.int64), a
+
+
+def refine_frame_offsets(kpts_2d, camera_params, seed, s0, rounds=4, h=0.02, stop=0.01, device=None, **fit_kw):
+    """Refines the cameras' frame offsets to a fraction of a frame from trajectory fits alone.
+
+    kpts_2d (T, J, 3, V) as recorded (not aligned), one column per camera of camera_params, in
+    sorted key order, which is refine.fit_trajectory's default view list; seed (T, J, 3): the
+    trajectory at camera 0's frames, which are the rig instants (s[0] = 0 is the gauge and stays);
+    s0 (V,) the offsets to start from, e.g. estimate_frame_offsets' info["s"], one per camera in the
+    same order.  Always all cameras: the whole frames are applied to kpts_2d's columns by position
+    and the fractions go to the fit's views by position, so a subset or another order would send
+    them to different cameras.  fit_kw goes to refine.fit_trajectory (weights, lambda_smooth,
+    huber_px, ...; not camera_indices).
+
+    Per round: split s (split_frame_offsets), align by the whole frames (apply_frame_offsets; a
+    fraction that crossed 0 or 1 is thereby re-split and re-aligned), fit with the fractions, and
+    sum info["dlag"][..., 0] over the valid joints on the host in ascending order: at a fitted
+    state that is the derivative of the minimised cost with respect to each offset.  A Newton step
+    on it follows, its Jacobian from central differences of that sum between 2·(V−1) further
+    fits at s_j ± h; the curvature the fit reports at fixed trajectory (dlag[..., 1]) overestimates
+    the reduced curvature badly and is not used.  A step is limited to half a frame.  At most
+    `rounds` rounds; stops on a step below `stop` frames.  Returns (s (V,) float64, info): "cost"
+    every round's summed cost and the final one, "step" every round's largest step, "fits" the
+    number of fits made."""
+    from . import refine
+    if "camera_indices" in fit_kw:
+        raise ValueError("refine_frame_offsets uses every camera of camera_params in sorted order; camera_indices is not taken")
+    kp = np.asarray(kpts_2d)
+    sd = np.asarray(seed)
+    s = np.array(s0, np.float64)
+    nv = len(camera_params)
+    if s.shape != (nv,):
+        raise ValueError(f"s0 must hold one offset per camera ({nv}), got shape {s.shape}")
+    if kp.ndim != 4 or kp.shape[-1] != nv:
+        raise ValueError(f"kpts_2d must be (T, J, 3, {nv}), one column per camera, got {kp.shape}")
+    fits = [0]
+
+    def reduced(sv):
+        n, a = split_frame_offsets(sv)
+        (k,), _ = apply_frame_offsets([kp], n, [3])
+        lo = int(n.max())
+        _, info = refine.fit_trajectory(np.ascontiguousarray(k), camera_params, sd[lo:lo + k.shape[0]],
+                                        frame_offsets=a, return_info=True, device=device,
+                                        **fit_kw)
+        fits[0] += 1
+        ok = np.flatnonzero(info["status"].reshape(-1) != 0x80)
+        dl = info["dlag"].reshape(-1, nv, 2)
+        ga = np.zeros(nv)
+        for p in ok:
+            ga = ga + dl[p, :, 0]
+        return ga, float(info["cost"].reshape(-1, 2)[ok, 1].sum())
+    costs, steps = [], []
+    for _ in range(int(rounds)):
+        g0, f0 = reduced(s)
+        costs.append(f0)
+        jac = np.zeros((nv - 1, nv - 1))
+        for j in range(1, nv):
+            sp, sm = s.copy(), s.copy()
+            sp[j] += h
+            sm[j] -= h
+            jac[:, j - 1] = (reduced(sp)[0][1:] - reduced(sm)[0][1:]) / (2 * h)
+        step = np.clip(-np.linalg.solve(jac, g0[1:]), -0.5, 0.5)
+        s[1:] += step
+        steps.append(float(np.abs(step).max()))
+        if steps[-1] < stop:
+            break
+    costs.append(reduced(s)[1])
+    return s, {"cost": costs, "step": steps, "fits": fits[0]}
