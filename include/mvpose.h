@@ -750,6 +750,101 @@ int mvp_associate_views(const float* kpts_dev, int T, int P, int J, int V, const
                         uint8_t* out_count_dev, double* out_affinity_dev, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Left/right label swaps per camera, undone by multi-view consistency (no reference counterpart;
+ * the reference takes the 2D detector's joint labels on trust).  The commonest gross error of a
+ * top-down detector is a left/right exchange in one camera: a person seen from behind is mirrored
+ * as a whole, a walker's legs are exchanged for a few frames.  For every frame, listed view and
+ * unit of symmetric joint pairs this block decides whether that view's labels are exchanged: the
+ * cameras must agree with each other (the epipolar constraint of the blocks above), and each
+ * camera with its own previous frame (continuity in the image).
+ *
+ * kpts_dev [T][J][3][V] float32, cams_dev, cam_idx_host / n_cam_idx = nv, 2 <= nv <= 8: exactly
+ * as for mvp_epipolar_lag_cost.
+ * pairs_host [NS][2] int32: the (left, right) joint of every symmetric pair, 1 <= NS <= 64,
+ *   indices in [0, J), all 2·NS of them distinct.
+ * unit_host [NS] int32 in [0, U), every unit used, 1 <= U <= NS: the pairs of one unit are
+ *   exchanged together (U = 1: the whole body).
+ *   Usable keypoint, ideal pixel x, F_ab, squared Sampson distance d²: exactly those of the
+ *     epipolar lag-cost scan.  View pairs p = (a, b), a < b, in its order, NP = nv·(nv−1)/2.
+ *     A keypoint that is usable by that rule but whose ideal pixel comes out NaN (the
+ *     undistortion overflows at absurd coordinates) counts as not usable here: it has no d².
+ *   Cost tables, float64, for frame t, unit u; τ = trunc_px, μ = motion_trunc_px, w =
+ *   motion_weight (the float32 values given, promoted to fp64):
+ *     Symmetric pair k is complete in view a at t when both of its keypoints are usable there;
+ *       n[t][u][a] = the number of complete pairs of unit u.
+ *     Epipolar tables: over the pairs k of unit u that are complete in a and in b at t with all
+ *       four d² finite and all four denominators non-zero (otherwise k contributes to neither),
+ *       in ascending k:
+ *         same[t][u][p]  = Σ min(d²(l_a, l_b), τ²) + min(d²(r_a, r_b), τ²)
+ *         cross[t][u][p] = Σ min(d²(l_a, r_b), τ²) + min(d²(r_a, l_b), τ²)
+ *     Motion tables: zero at t = 0; for t >= 1 over the pairs complete in a at both t and t − 1,
+ *       with the raw float32 pixel positions q promoted to fp64:
+ *         keep[t][u][a]   = w · Σ min(|q_l(t) − q_l(t−1)|², μ²) + min(|q_r(t) − q_r(t−1)|², μ²)
+ *         change[t][u][a] = w · Σ min(|q_l(t) − q_r(t−1)|², μ²) + min(|q_r(t) − q_l(t−1)|², μ²)
+ *     Prior table: prior[t][u][a] = swap_prior_px² · n[t][u][a].
+ *     The products are done when the tables are built: the solver below only adds and compares,
+ *     so FMA contraction cannot change its bits.  The tables themselves are fp64 with contraction
+ *     allowed and carry no bit contract, but no atomics: the same inputs give the same bits.
+ *   State, per unit: s in [0, 2^nv), bit a set when view a's labels of that unit are exchanged at
+ *     t.  Units are solved independently.
+ *   Frame cost E(t, s), accumulated in this order: start at 0; + prior[t][u][a] for a ascending
+ *     over the set bits of s; then for p ascending + same[t][u][p] when bits a and b of s are
+ *     equal, else + cross[t][u][p].
+ *   Recursion: D_0(s) = E(0, s).  For t >= 1 start from G = D_{t−1} and flip(s) = 0.  For each
+ *     view a = 0 .. nv−1 in turn, with s' = s xor 2^a:
+ *         k = G(s) + keep[t][u][a],   c = G(s') + change[t][u][a];
+ *     when c < k (strictly) the new G(s) = c and the new flip(s) = flip_old(s') | 2^a, otherwise
+ *     the new G(s) = k and flip(s) stays.  Every state of a pass reads the old G and flip.  Then
+ *     D_t(s) = G(s) + E(t, s) and bp[t][s] = flip(s), one byte.
+ *   Answer: s_{T−1} is the smallest s that attains min D_{T−1}; s_{t−1} = s_t xor bp[t][s_t].
+ *   Apply: out_kpts is a copy of kpts in which, for every set bit of s_t, the full (x, y, conf)
+ *     records of l and r of the unit's pairs are exchanged in that view's column (columns that
+ *     cam_idx does not list are copied).  An optional second array [T][V][J][C] float64 (the
+ *     heatmaps_2d layout, C = 6) is treated the same way.  Applying the same mask twice restores
+ *     the input's bits.
+ * Consequences: complementing s in all views leaves the epipolar terms unchanged; the prior (a
+ * detector is more often right than wrong) and the motion terms then fix which side is "left".
+ * With two views and a mirror that begins after frame 0, the motion term singles out the view
+ * whose labels jumped.  A unit with no data at a frame carries its state through unchanged: ties
+ * keep.  Pairs a few pixels apart (eyes, ears) carry no evidence and are best left out.
+ *
+ * mvp_label_swap_plan : checks (T, J, nv, NS, U) and reports the workspace bytes that serve both
+ *   mvp_label_swap_costs and mvp_label_swap_solve (may be NULL).
+ * mvp_label_swap_solve_plan : checks (T, U, nv) and reports the bytes mvp_label_swap_solve alone
+ *   needs (may be NULL), for tables that do not come from mvp_label_swap_costs.
+ * mvp_label_swap_costs : the tables.  workspace_dev >= the plan's bytes, owned by the caller (its
+ *   contents are scratch).  out_same_dev, out_cross_dev [T][U][NP] float64; out_keep_dev,
+ *   out_change_dev, out_prior_dev [T][U][nv] float64; out_n_dev [T][U][nv] int32 or NULL.
+ * mvp_label_swap_solve : the recursion and the backtrack on tables in that layout (they need not
+ *   come from mvp_label_swap_costs).  workspace_dev holds bp: at least U · ceil256(T · 2^nv)
+ *   bytes, which the plan's bytes cover.  out_swap_dev [T][U] uint8 = s_t per unit;
+ *   out_cost_dev [U] float64 or NULL = min D_{T−1}.  One wavefront per unit runs the frames in
+ *   sequence: latency-bound by construction.
+ * mvp_label_swap_apply : gauss_dev and out_gauss_dev both NULL or both given; the outputs must not
+ *   be the inputs; cam_idx_host must not list a column twice.
+ * All require T >= 1, J >= 2, T·J < 2^31, 2 <= nv <= 8; the costs also trunc_px and
+ * motion_trunc_px finite and > 0, motion_weight and swap_prior_px finite and >= 0, min_conf not
+ * NaN.  Argument errors return MVP_ERR_ARG before any device work.  Stream-ordered: no host
+ * synchronisation, no allocation and no host decision inside the calls.
+ * ------------------------------------------------------------------------- */
+int mvp_label_swap_plan(int T, int J, int n_cam_idx, int n_pairs, int n_units, int64_t* workspace_bytes);
+int mvp_label_swap_solve_plan(int T, int n_units, int n_cam_idx, int64_t* workspace_bytes);
+int mvp_label_swap_costs(const float* kpts_dev, int T, int J, int V, const double* cams_dev, int n_cams,
+                         const int* cam_idx_host, int n_cam_idx, const int* pairs_host, int n_pairs,
+                         const int* unit_host, int n_units, float min_conf, float trunc_px, float motion_trunc_px,
+                         float motion_weight, float swap_prior_px, void* workspace_dev, int64_t workspace_bytes,
+                         double* out_same_dev, double* out_cross_dev, double* out_keep_dev, double* out_change_dev,
+                         double* out_prior_dev, int32_t* out_n_dev, void* stream);
+int mvp_label_swap_solve(const double* same_dev, const double* cross_dev, const double* keep_dev,
+                         const double* change_dev, const double* prior_dev, int T, int n_units, int n_cam_idx,
+                         void* workspace_dev, int64_t workspace_bytes, uint8_t* out_swap_dev, double* out_cost_dev,
+                         void* stream);
+int mvp_label_swap_apply(const float* kpts_dev, const double* gauss_dev, int T, int J, int V, int C,
+                         const int* cam_idx_host, int n_cam_idx, const int* pairs_host, int n_pairs,
+                         const int* unit_host, int n_units, const uint8_t* swap_dev, float* out_kpts_dev,
+                         double* out_gauss_dev, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Tracking of people through time: which group of frame t is the person of which group of an
  * earlier frame, so that a person keeps one number through the recording and through short
  * dropouts.  No reference counterpart (the reference handles one person per camera).  The input is

@@ -119,6 +119,15 @@ SIGNATURES = {
     "mvp_associate_views": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_float,
                                     c_float, c_float, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "mvp_label_swap_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_int64)]),
+    "mvp_label_swap_solve_plan": (c_int, [c_int, c_int, c_int, P(c_int64)]),
+    "mvp_label_swap_costs": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(c_int), c_int, P(c_int), c_int,
+                                     P(c_int), c_int, c_float, c_float, c_float, c_float, c_float, c_void_p, c_int64,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_label_swap_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                     c_int64, c_void_p, c_void_p, c_void_p]),
+    "mvp_label_swap_apply": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, P(c_int), c_int, P(c_int), c_int,
+                                     P(c_int), c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_track_people_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, P(c_int)]),
     "mvp_track_people": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -58,7 +58,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                              checkerboard_display_parameter_yaml="./checkerboard_display_parameters.yaml",
                              origin_camera_idx=0, script_path=None, project_dir="", recording_length_seconds=10,
                              keep_unsynced_files=False, triangulation="reference", inlier_px=10.0,
-                             min_confidence=0.0, refine=None, cov_floor=1.0, sync_from_pose=False, max_lag=60):
+                             min_confidence=0.0, refine=None, cov_floor=1.0, sync_from_pose=False, max_lag=60,
+                             fix_label_swaps=None):
     """triangulation / inlier_px / min_confidence (no reference counterpart): "reference" (default)
     triangulates from cameras [0, 1] and writes exactly the reference's files; "all_views" and
     "robust" use every camera in camera_names (estimate_pose_from_video), record the three
@@ -72,7 +73,13 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
     from the 2D keypoints over lags of -max_lag..max_lag frames (estimate_pose_from_video's
     sync="pose"); kpts_2d.npy, heatmaps_2d.npy and everything after them then hold the frames cut
     to the common instants, frame_offsets.npy (V,) int64 is written too, and recording_log.yaml
-    records the offsets, max_lag and the rejected pairs under "sync"."""
+    records the offsets, max_lag and the rejected pairs under "sync".
+    fix_label_swaps (no reference counterpart): "limbs" or "body" finds and undoes the detector's
+    per-camera left/right label exchanges (estimate_pose_from_video's fix_swaps) after the
+    synchronisation and before the triangulation; kpts_2d.npy, heatmaps_2d.npy and everything
+    after them hold the fixed labels, label_swaps.npy (T, U) uint8 is written too, and
+    recording_log.yaml records the preset and the number of exchanged (frame, unit, camera)
+    entries under "fix_label_swaps"."""
     if refine not in (None, "unit", "conf", "heatmap"):
         raise ValueError(f"refine {refine!r}: None, 'unit', 'conf' or 'heatmap'")
     from .pose_estimation import estimate_pose_from_video
@@ -97,6 +104,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
         robust_kw.update({"refine": refine, "cov_floor": cov_floor, "return_info": True})
     if sync_from_pose:
         robust_kw.update({"sync": "pose", "max_lag": max_lag, "return_info": True})
+    if fix_label_swaps is not None:
+        robust_kw.update({"fix_swaps": fix_label_swaps, "return_info": True})
     kpts_2d, heatmaps, kpts_3d, *info = estimate_pose_from_video(
         camera_names, recording_paths, estimator_model, detector_model=detector_model, model_yaml=model_yaml,
         start_end_frames=[0, -1], confidence=0,
@@ -127,6 +136,12 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                        "offsets": [int(o) for o in info[0]["frame_offsets"]],
                        "rejected_pairs": [[camera_names[a], camera_names[b], r]
                                           for (a, b), r in zip(pair_info["pairs"], pair_info["reason"]) if r]}
+    if fix_label_swaps is not None:
+        swap = info[0]["label_swaps"]
+        log["label_swaps"] = str(os.path.join(recordings_folder, "label_swaps.npy"))
+        extra["label_swaps"] = swap
+        log["fix_label_swaps"] = {"units": fix_label_swaps,
+                                  "exchanged": int(np.unpackbits(np.ascontiguousarray(swap)).sum())}
     with open(os.path.join(recordings_folder, "recording_log.yaml"), "w") as f:
         yaml.dump(log, f)
     if kpts_2d is not None:
@@ -143,7 +158,7 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
 def record_and_estimate_pose_parser(extensions=False):
     """Flags of record_and_estimate_pose.py:63-78; extensions=True (what the command line uses)
     adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence,
-    --refine, --cov_floor, --sync_from_pose, --max_lag."""
+    --refine, --cov_floor, --sync_from_pose, --max_lag, --fix_label_swaps."""
     p = argparse.ArgumentParser()
     p.add_argument("--camera_names", nargs="+", required=True, help="List of camera names")
     p.add_argument("--estimator_model")
@@ -167,6 +182,7 @@ def record_and_estimate_pose_parser(extensions=False):
         p.add_argument("--cov_floor", type=float)
         p.add_argument("--sync_from_pose", action="store_true")   # frame offsets from the 2D keypoints
         p.add_argument("--max_lag", type=int)
+        p.add_argument("--fix_label_swaps", choices=["limbs", "body"])   # undo per-camera left/right exchanges
     return p
 
 

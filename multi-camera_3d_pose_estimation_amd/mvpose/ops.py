@@ -439,6 +439,131 @@ def associate_views(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[in
     return group, count, aff, pairs
 
 
+def _swap_lists(pairs, units):
+    """pairs (NS, 2), units (NS,) -> (NS, U, the two ctypes int arrays); the library checks the values."""
+    pairs = np.asarray(pairs, dtype=np.int64)
+    units = np.asarray(units, dtype=np.int64).ravel()
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or len(pairs) != len(units) or len(units) == 0:
+        raise ValueError(f"pairs must be (NS, 2) and units (NS,), NS >= 1; got {pairs.shape} and {units.shape}")
+    ns = len(units)
+    return (ns, int(units.max()) + 1, (ctypes.c_int * (2 * ns))(*[int(j) for j in pairs.ravel()]),
+            (ctypes.c_int * ns)(*[int(u) for u in units]))
+
+
+def label_swap_plan(T: int, J: int, nv: int, n_pairs: int, n_units: int) -> int:
+    """The workspace bytes that serve label_swap_costs and label_swap_solve for (T, J, nv, NS, U)
+    (mvp_label_swap_plan, which refuses what the calls refuse of these)."""
+    nbytes = ctypes.c_int64(0)
+    call("mvp_label_swap_plan", int(T), int(J), int(nv), int(n_pairs), int(n_units), ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def label_swap_solve_plan(T: int, n_units: int, nv: int) -> int:
+    """The workspace bytes of label_swap_solve alone for (T, U, nv) (mvp_label_swap_solve_plan, which
+    refuses what the call refuses of these)."""
+    nbytes = ctypes.c_int64(0)
+    call("mvp_label_swap_solve_plan", int(T), int(n_units), int(nv), ctypes.byref(nbytes))
+    return nbytes.value
+
+
+def label_swap_costs(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], pairs, units, *,
+                     min_conf: float = 0.0, trunc_px: float = 20.0, motion_trunc_px: float = 40.0,
+                     motion_weight: float = 1.0, swap_prior_px: float = 2.0, return_n: bool = False):
+    """The cost tables of the left/right label-swap decision (mvp_label_swap_costs; the model is
+    stated in include/mvpose.h; no reference counterpart).
+
+    kpts (T, J, 3, V) float32 and cams (n_cams, 40) float64 on the GPU, cam_idx as for
+    epipolar_lag_cost; pairs (NS, 2): the (left, right) joint of every symmetric pair; units (NS,):
+    the unit each pair is exchanged with.  Returns (same, cross (T, U, NP) float64, keep, change,
+    prior (T, U, NV) float64) and, with return_n, the complete-pair counts n (T, U, NV) int32 as a
+    sixth.  The workspace is a torch.empty on the call's stream, sized by label_swap_plan."""
+    V, lead, _, ci = _tri_args(kpts, cams, cam_idx)
+    if len(lead) != 2:
+        raise ValueError(f"kpts must be (T, J, 3, V), got {tuple(kpts.shape)}")
+    T, J = int(lead[0]), int(lead[1])
+    nv = len(ci)
+    ns, U, cp, cu = _swap_lists(pairs, units)
+    nbytes = label_swap_plan(T, J, nv, ns, U)
+    dev = kpts.device
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    n_vp = nv * (nv - 1) // 2
+    same, cross = (torch.empty((T, U, n_vp), dtype=torch.float64, device=dev) for _ in range(2))
+    keep, change, prior = (torch.empty((T, U, nv), dtype=torch.float64, device=dev) for _ in range(3))
+    n = torch.empty((T, U, nv), dtype=torch.int32, device=dev) if return_n else None
+    call("mvp_label_swap_costs", ptr(kpts), T, J, V, ptr(cams), cams.shape[0], ci, nv, cp, ns, cu, U, float(min_conf),
+         float(trunc_px), float(motion_trunc_px), float(motion_weight), float(swap_prior_px), ptr(work), int(nbytes),
+         ptr(same), ptr(cross), ptr(keep), ptr(change), ptr(prior), ptr(n), stream(dev))
+    return (same, cross, keep, change, prior, n) if return_n else (same, cross, keep, change, prior)
+
+
+def label_swap_solve(same: torch.Tensor, cross: torch.Tensor, keep: torch.Tensor, change: torch.Tensor,
+                     prior: torch.Tensor):
+    """The label-swap recursion and backtrack on given tables (mvp_label_swap_solve; include/mvpose.h):
+    same, cross (T, U, NP) and keep, change, prior (T, U, NV) float64 on the GPU, NP = NV·(NV−1)/2.
+    Returns (swap (T, U) uint8: bit a set where view a's labels of the unit are exchanged, cost (U,)
+    float64: the minimum of the objective).  The solver only adds and compares: the same tables
+    give the same answer as any implementation that adds in the stated order."""
+    for name, t in (("same", same), ("cross", cross), ("keep", keep), ("change", change), ("prior", prior)):
+        _require(t, torch.float64, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name} must be (T, U, n), got {tuple(t.shape)}")
+    T, U, nv = (int(d) for d in keep.shape)
+    n_vp = nv * (nv - 1) // 2
+    if not (same.shape == cross.shape == (T, U, n_vp) and change.shape == prior.shape == (T, U, nv)):
+        raise ValueError(f"tables disagree: same {tuple(same.shape)}, cross {tuple(cross.shape)}, keep "
+                         f"{tuple(keep.shape)}, change {tuple(change.shape)}, prior {tuple(prior.shape)}")
+    dev = keep.device
+    nbytes = label_swap_solve_plan(T, U, nv)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    swap = torch.empty((T, U), dtype=torch.uint8, device=dev)
+    cost = torch.empty((U,), dtype=torch.float64, device=dev)
+    call("mvp_label_swap_solve", ptr(same), ptr(cross), ptr(keep), ptr(change), ptr(prior), T, U, nv, ptr(work),
+         int(nbytes), ptr(swap), ptr(cost), stream(dev))
+    return swap, cost
+
+
+def label_swap_apply(kpts: torch.Tensor, swap: torch.Tensor, cam_idx: Sequence[int], pairs, units, *, gauss=None):
+    """kpts (T, J, 3, V) float32 with the labels exchanged where swap (T, U) uint8 says so
+    (mvp_label_swap_apply): for every set bit a of swap[t, u], the (x, y, conf) records of the left
+    and right joint of unit u's pairs change places in column cam_idx[a].  gauss (T, V, J, C) float64
+    or None is treated the same way.  Returns (kpts_out, gauss_out or None), new tensors; applying
+    the same mask to them restores the input's bits."""
+    _require(kpts, torch.float32, "kpts")
+    _require(swap, torch.uint8, "swap")
+    if kpts.dim() != 4 or kpts.shape[2] != 3:
+        raise ValueError(f"kpts must be (T, J, 3, V), got {tuple(kpts.shape)}")
+    T, J, _, V = (int(d) for d in kpts.shape)
+    ns, U, cp, cu = _swap_lists(pairs, units)
+    if tuple(swap.shape) != (T, U):
+        raise ValueError(f"swap must be (T, U) = {(T, U)}, got {tuple(swap.shape)}")
+    C = 0
+    if gauss is not None:
+        _require(gauss, torch.float64, "gauss")
+        if gauss.dim() != 4 or tuple(gauss.shape[:3]) != (T, V, J):
+            raise ValueError(f"gauss must be (T, V, J, C) = {(T, V, J)} + (C,), got {tuple(gauss.shape)}")
+        C = int(gauss.shape[3])
+    ci = (ctypes.c_int * len(cam_idx))(*[int(c) for c in cam_idx])
+    out = torch.empty_like(kpts)
+    gout = torch.empty_like(gauss) if gauss is not None else None
+    call("mvp_label_swap_apply", ptr(kpts), ptr(gauss), T, J, V, C, ci, len(ci), cp, ns, cu, U, ptr(swap), ptr(out),
+         ptr(gout), stream(kpts.device))
+    return out, gout
+
+
+def fix_label_swaps(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], pairs, units, *, gauss=None,
+                    min_conf: float = 0.0, trunc_px: float = 20.0, motion_trunc_px: float = 40.0,
+                    motion_weight: float = 1.0, swap_prior_px: float = 2.0):
+    """Find and undo the left/right label exchanges of every listed view: label_swap_costs,
+    label_swap_solve, label_swap_apply on one stream, no synchronisation between them.  Returns
+    (kpts_fixed, gauss_fixed or None, swap (T, U) uint8)."""
+    tables = label_swap_costs(kpts, cams, cam_idx, pairs, units, min_conf=min_conf, trunc_px=trunc_px,
+                              motion_trunc_px=motion_trunc_px, motion_weight=motion_weight,
+                              swap_prior_px=swap_prior_px)
+    swap, _ = label_swap_solve(*tables)
+    fixed, gfixed = label_swap_apply(kpts, swap, cam_idx, pairs, units, gauss=gauss)
+    return fixed, gfixed, swap
+
+
 def track_people_plan(M: int, T: int, G: int, J: int, max_gap: int = 5) -> int:
     """The LDS bytes of track_people's workgroup for (M, T, G, J, max_gap) (mvp_track_people_plan,
     which refuses what the call refuses of these)."""

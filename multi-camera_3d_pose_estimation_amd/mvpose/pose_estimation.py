@@ -27,6 +27,7 @@ import torch
 import yaml
 
 from . import geometry, ops
+from . import swaps as label_swaps
 from . import sync as frame_sync
 from .estimator import BatchPoseEstimator
 from .hrnet import N_JOINTS
@@ -352,7 +353,8 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
 def estimate_pose_from_video(camera_names, recording_paths, model, detector_model="coco_base", model_yaml="",
                              start_end_frames=(0, -1), confidence=0, extrinsic_params_dir="",
                              recompute_kpts_2d=True, triangulation="reference", inlier_px=10.0, min_conf=0.0,
-                             return_info=False, refine=None, cov_floor=1.0, sync=None, max_lag=60):
+                             return_info=False, refine=None, cov_floor=1.0, sync=None, max_lag=60,
+                             fix_swaps=None):
     """pose_estimation.py:259-327.  recompute_kpts_2d replaces the reference's interactive
     y/n prompt when kpts_2d.npy already exists (:287-289).
 
@@ -369,12 +371,20 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
     frames), kpts_2d and heatmaps_2d are cut to the common instants (sync.apply_frame_offsets) and
     the aligned arrays are triangulated and returned.  ValueError, naming the cameras, when an
     offset cannot be fixed.  info then also holds "frame_offsets" (V,) int64, "frame_first" (each
-    camera's first kept frame) and "sync_pairs", estimate_frame_offsets' pair table."""
+    camera's first kept frame) and "sync_pairs", estimate_frame_offsets' pair table.
+
+    fix_swaps: None (default: the detector's left/right labels are taken as they are), "limbs" or
+    "body" (swaps.PRESETS): after synchronisation and before triangulation, the left/right label
+    exchanges of every camera in camera_names are found and undone (swaps.fix_label_swaps) in
+    kpts_2d and heatmaps_2d; the fixed arrays are triangulated and returned.  info then also holds
+    "label_swaps" (T, U) uint8: bit v set where camera v's labels of unit u were exchanged."""
     if triangulation not in TRIANGULATION_METHODS:
         raise ValueError(f"triangulation {triangulation!r}: one of {TRIANGULATION_METHODS}")
     _check_refine(refine)
     if sync not in SYNC_MODES:
         raise ValueError(f"sync {sync!r}: one of {SYNC_MODES}")
+    if fix_swaps is not None and fix_swaps not in label_swaps.PRESETS:
+        raise ValueError(f"fix_swaps {fix_swaps!r}: None or one of {tuple(label_swaps.PRESETS)}")
     index_name, _origin = geometry.load_camera_names(extrinsic_params_dir)
     name_index = {v: k for k, v in index_name.items()}
     camera_indices = [name_index[n] for n in camera_names]
@@ -406,6 +416,10 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
             raise ValueError(f"sync='pose': no frame offset for camera(s) {lost} (rejected pairs: {why})")
         (kpts_2d, heatmaps), first = frame_sync.apply_frame_offsets([kpts_2d, heatmaps], offsets, (3, 1))
         sync_info = {"frame_offsets": offsets, "frame_first": first, "sync_pairs": pair_info}
+    if fix_swaps is not None:
+        kpts_2d, heatmaps, swap = label_swaps.fix_label_swaps(kpts_2d, camera_params, units=fix_swaps,
+                                                              heatmaps_2d=heatmaps, min_conf=min_conf)
+        sync_info["label_swaps"] = swap
     if triangulation == "reference" and refine is None:
         listed = [0, 1]
         kpts_3d = get_pose_3D(camera_params, kpts_2d, camera_indices=listed)
