@@ -133,6 +133,50 @@ int mvp_triangulate_robust(const float* kpts_dev, int64_t n_points, int V, const
                            float* out_err_dev /* [n][n_cam_idx], may be NULL */, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * mvp_triangulate_peaks — mvp_triangulate_robust over up to MVP_MAX_PEAKS 2D candidates per view
+ * (the modes of a heatmap, mvp_heatmap_peaks), choosing one candidate per inlier view.  No
+ * reference counterpart.  With M = 1 it is mvp_triangulate_robust: xyz and mask bit for bit.
+ *
+ * peaks_dev : [n_points][M][3][V] float32, rows x, y, score; slot m of a point has the kpts
+ * layout.  cams_dev, cam_idx_host / n_cam_idx, the undistortion and the reprojection error are
+ * mvp_triangulate_robust's.
+ *   Valid candidate (view i, slot m): x and y finite, score not NaN and >= min_conf, undistorted
+ *     point finite.  Valid view: a view with at least one valid candidate.  Top candidate of a
+ *     view: its valid candidate with the lowest slot.
+ *   Step A: fewer than 2 valid views -> xyz NaN, mask 0, every sel -1, errors NaN.  Otherwise the
+ *     DLT over the top candidates of all valid views, its float32 xyz, and each valid view's error
+ *     (top candidate) against (x, y, z, 1); if every one is <= inlier_px the point is done,
+ *     mask = the valid views, sel = their top slots.
+ *   Step B (other points): hypotheses in lexicographic order of (a, b, ma, mb), a < b valid views,
+ *     ma / mb valid candidates of a / b; each is the fp64 null vector of the 4x4 two-view DLT of
+ *     that candidate pair.  Against a hypothesis every valid view (a and b like any other) chooses
+ *     its valid candidate with the smallest error, ties to the lower slot, and is an inlier when
+ *     that error is <= inlier_px.  Best = most inliers, then the larger sum of the inliers' chosen
+ *     scores (f32, ascending view position), then the first hypothesis.  Best count < 2: the point
+ *     fails as in step A.  Otherwise the final DLT over the inlier views with their chosen
+ *     candidates: mask = that set, sel = those slots.
+ * The float32 xyz equals, bit for bit, OpenCV 4.9's triangulation (Jacobi SVD DLT +
+ * convertPointsFromHomogeneous) over exactly the masked views' selected candidates in ascending
+ * position (mvp_triangulate_robust's contract and solver).
+ *
+ * 1 <= M <= MVP_MAX_PEAKS; inlier_px finite and > 0; min_conf not NaN.
+ * out_xyz_dev  : [n_points][3] float32.
+ * out_mask_dev : [n_points] uint8, bit i = view i (cam_idx[i]) used.
+ * out_sel_dev  : [n_points][n_cam_idx] int8, the slot used by view i, -1 for a view not in the mask.
+ * out_err_dev  : optional [n_points][n_cam_idx] float32 against the final float32 point (w = 1):
+ *                a masked view's selected candidate; for a valid view outside the mask the
+ *                smallest error over its valid candidates; NaN for invalid views and failed points.
+ * out_kpts_dev : optional [n_points][3][V] float32, the kpts layout: column cam_idx[i] of a masked
+ *                view holds its selected candidate, every other column slot 0 unchanged.
+ * ------------------------------------------------------------------------- */
+#define MVP_MAX_PEAKS 4
+
+int mvp_triangulate_peaks(const float* peaks_dev, int64_t n_points, int M, int V, const double* cams_dev,
+                          int n_cams, const int* cam_idx_host, int n_cam_idx, float inlier_px, float min_conf,
+                          float* out_xyz_dev, uint8_t* out_mask_dev, int8_t* out_sel_dev,
+                          float* out_err_dev /* may be NULL */, float* out_kpts_dev /* may be NULL */, void* stream);
+
+/* ---------------------------------------------------------------------------
  * mvp_triangulate_refine — maximum-likelihood N-view triangulation from a seed, with the point's
  * 3D covariance.  No reference counterpart.  (The reference's SGD scores every camera against
  * camera 0's Gaussian, finding F5; here each camera is scored against its own.)
@@ -243,6 +287,26 @@ int mvp_heatmap_decode(const float* hm_dev, const float* hm_flip_dev, int N, int
                        const int* flip_idx_host, int shift, const float* center_scale_dev, int input_w, int input_h,
                        float* avg_dev, float* kpts_dev, float* scores_dev, int32_t* argmax_dev, float* kpts_tkv_dev,
                        int V, void* stream);
+/* mvp_heatmap_peaks: up to max_peaks local maxima of every map, each decoded as
+ *   mvp_heatmap_decode decodes its argmax (no reference counterpart; the candidates of
+ *   mvp_triangulate_peaks).  hm_dev [N][K][H][W] f32: the maps decoding looks at, i.e.
+ *   mvp_heatmap_decode's avg_dev, crops ordered (t, v); center_scale_dev, input_w, input_h as there.
+ *   Cell i = y*W + x with value v is a peak when v is no NaN, v > thr, and for every other
+ *   in-bounds cell n (value u) of the (2·radius+1)² window around it: u is NaN, or v > u, or
+ *   v == u and i < n.  Peaks are ordered by descending v, ties by ascending i (the decode's
+ *   argmax order: on a NaN-free map whose maximum exceeds thr the first peak is the argmax cell);
+ *   peak r > 0 is kept only if v_r >= min_rel * v_0 (f32 product); the first
+ *   min(count, max_peaks) are written.  A written peak is decoded with the decode's arithmetic
+ *   (val <= 0 -> -1, +-0.25 sign step inside 1 < px < W-1, 1 < py < H-1, f32 scale factor, fp64
+ *   restore rounded to f32); its score is v.
+ *   peaks_dev [N/V][K][max_peaks][3][V] f32, rows x, y, score in image pixels: peaks[:, :, m] has
+ *   the kpts_tkv layout; unfilled slots hold x = y = NaN, score 0.  counts_dev (nullable)
+ *   [N/V][K][V] int32, the peaks written.
+ *   1 <= max_peaks <= MVP_MAX_PEAKS, 1 <= radius <= 3, thr not NaN, 0 <= min_rel <= 1, V >= 1
+ *   dividing N, H*W <= 65536, K <= 32. */
+int mvp_heatmap_peaks(const float* hm_dev, int N, int K, int H, int W, const float* center_scale_dev, int input_w,
+                      int input_h, int max_peaks, int radius, float thr, float min_rel, int V, float* peaks_dev,
+                      int32_t* counts_dev, void* stream);
 int mvp_warp_is_separable(const double* minv_host, int img_h, int img_w, int* separable_out);
 /* revert_heatmap only (not on the hot path, which fuses it into the moments): each crop's
  * K maps [N][K][h][w] f32 warped to the image, out [N][K][img_h][img_w] f32 — cv2.warpAffine

@@ -20,7 +20,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "mvp_common.h"
+#include "heatmap_decode.h"
 
 namespace {
 
@@ -135,14 +135,6 @@ __device__ __forceinline__ float avg_at(const DecodeParams& p, const float* h, c
     return __fmul_rn(__fadd_rn(a, b), 0.5f);
 }
 
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) {
-    // np.argmax: first occurrence of the max; NaN counts as the max (first NaN wins)
-    const bool vn = isnan(v), bn = isnan(bv);
-    if (bn) return vn && i < bi;
-    if (vn) return true;
-    return v > bv || (v == bv && i < bi);
-}
-
 __global__ __launch_bounds__(kBlock) void decode_kernel(DecodeParams p) {
     const int lane = threadIdx.x & 63;
     const long map = (long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -209,39 +201,18 @@ __global__ __launch_bounds__(kBlock) void decode_kernel(DecodeParams p) {
         }
     }
     if (lane != 0) return;
-    const int py = bi / p.W, px = bi - (bi / p.W) * p.W;
-    float kx = (float)px, ky = (float)py;
-    if (!(bv > 0.f)) {  // locs[vals <= 0.] = -1 (NaN > 0 is false but NaN <= 0 is false too)
-        if (!isnan(bv)) {
-            kx = -1.f;
-            ky = -1.f;
-        }
-    }
-    const int ipx = (int)kx, ipy = (int)ky;
-    if (1 < ipx && ipx < p.W - 1 && 1 < ipy && ipy < p.H - 1) {
-        const float dx = __fsub_rn(avg_at(p, h, hf, ipy, ipx + 1), avg_at(p, h, hf, ipy, ipx - 1));
-        const float dy = __fsub_rn(avg_at(p, h, hf, ipy + 1, ipx), avg_at(p, h, hf, ipy - 1, ipx));
-        const float sgx = dx > 0.f ? 1.f : (dx < 0.f ? -1.f : (isnan(dx) ? dx : 0.f));
-        const float sgy = dy > 0.f ? 1.f : (dy < 0.f ? -1.f : (isnan(dy) ? dy : 0.f));
-        kx = __fadd_rn(kx, __fmul_rn(sgx, 0.25f));
-        ky = __fadd_rn(ky, __fmul_rn(sgy, 0.25f));
-    }
-    // * scale_factor (input_size / heatmap_size, f32)
-    kx = __fmul_rn(kx, (float)(p.in_w / p.W));
-    ky = __fmul_rn(ky, (float)(p.in_h / p.H));
-    // keypoints / input_size * input_scale + input_center - 0.5 * input_scale (f64, stored f32)
-    const float* cs = p.cs + 4 * n;
-    const double ox = (double)kx / p.in_w * (double)cs[2] + (double)cs[0] - 0.5 * (double)cs[2];
-    const double oy = (double)ky / p.in_h * (double)cs[3] + (double)cs[1] - 0.5 * (double)cs[3];
-    p.kpts[2 * map + 0] = (float)ox;
-    p.kpts[2 * map + 1] = (float)oy;
+    float ox, oy;
+    decode_cell(bi, bv, p.H, p.W, p.in_w, p.in_h, p.cs + 4 * n,
+                [&](int y, int x) { return avg_at(p, h, hf, y, x); }, ox, oy);
+    p.kpts[2 * map + 0] = ox;
+    p.kpts[2 * map + 1] = oy;
     p.scores[map] = bv;
     if (p.amax) p.amax[map] = bi;
     if (p.tkv) {  // crops ordered (t, v): pose_estimation.py:135 stacks [x, y, score] per camera on the last axis
         const int t = n / p.V, v = n - (n / p.V) * p.V;
         float* o = p.tkv + (((long)t * p.K + k) * 3) * p.V + v;
-        o[0] = (float)ox;
-        o[p.V] = (float)oy;
+        o[0] = ox;
+        o[p.V] = oy;
         o[2 * p.V] = bv;
     }
 }

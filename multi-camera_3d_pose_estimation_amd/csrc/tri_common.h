@@ -544,6 +544,19 @@ __device__ __forceinline__ bool view_usable(float x, float y, float conf, float 
     return isfinite(x) && isfinite(y) && !isnan(conf) && conf >= min_conf;
 }
 
+// Reprojection error of view i against homogeneous X (the robust and the peak-selecting kernels'
+// rule, mvpose.h): q = P_i·X in fp64; +inf unless q2·X3 > 0 (in front of the camera), else the
+// distance of (q0/q2, q1/q2) to the f32 undistorted point.
+__device__ __forceinline__ double reprojection_error(const double* __restrict__ P, const double (&X)[4], float ux,
+                                                     float uy) {
+    const double q0 = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3] * X[3];
+    const double q1 = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7] * X[3];
+    const double q2 = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11] * X[3];
+    if (!(q2 * X[3] > 0)) return (double)INFINITY;
+    const double dx = q0 / q2 - (double)ux, dy = q1 / q2 - (double)uy;
+    return sqrt(dx * dx + dy * dy);
+}
+
 // ----------------------------------------------------------------- host side
 // The argument checks every N-view entry point opens with; `fn`, the entry point's name, prefixes
 // each message.  Returns the listed cameras.  No device call: the callers' n_points == 0 return

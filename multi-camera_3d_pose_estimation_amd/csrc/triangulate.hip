@@ -7,6 +7,8 @@
 //   triangulate_tol.hip     MVP_TRI_TOLERANCE: the certified two-camera solver, its exact fallback
 //                           launch and per-stream list; mvp_triangulate_fallback_total
 //   triangulate_robust.hip  outlier-view rejection; mvp_triangulate_robust
+//   triangulate_peaks.hip   the robust scheme over up to MVP_MAX_PEAKS candidates per view, choosing
+//                           one per inlier view; mvp_triangulate_peaks
 //   triangulate_refine.hip  Levenberg-Marquardt refinement + covariance; mvp_triangulate_refine
 #pragma clang fp contract(off)
 

@@ -22,17 +22,7 @@ namespace {
 //   * step B (the 4x4 DLT of every pair of valid views, one-sided Jacobi: accurate whatever the
 //     pair's conditioning; only selects, no bit contract) is entered under a wave ballot: a wave
 //     whose points all pass step A never runs it.
-// Reprojection error of view i against homogeneous X: q = P_i·X in fp64; +inf unless q2·X3 > 0
-// (in front of the camera), else the distance of (q0/q2, q1/q2) to the f32 undistorted point.
-__device__ __forceinline__ double reprojection_error(const double* __restrict__ P, const double (&X)[4], float ux,
-                                                     float uy) {
-    const double q0 = P[0] * X[0] + P[1] * X[1] + P[2] * X[2] + P[3] * X[3];
-    const double q1 = P[4] * X[0] + P[5] * X[1] + P[6] * X[2] + P[7] * X[3];
-    const double q2 = P[8] * X[0] + P[9] * X[1] + P[10] * X[2] + P[11] * X[3];
-    if (!(q2 * X[3] > 0)) return (double)INFINITY;
-    const double dx = q0 / q2 - (double)ux, dy = q1 / q2 - (double)uy;
-    return sqrt(dx * dx + dy * dy);
-}
+// Reprojection error of a view against a homogeneous X: reprojection_error (tri_common.h).
 
 // NV = 8 left to the compiler takes 256 VGPRs + 17 AGPRs = 1 wave per SIMD; held at 2 waves
 // (256 VGPRs, 80 B/lane of scratch) it measured 0.199 against 0.285 ms per 1 M clean points.

@@ -44,6 +44,8 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_robust": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_float, c_float,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mvp_triangulate_peaks": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, P(c_int), c_int, c_float,
+                                      c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mvp_triangulate_refine": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, P(c_int), c_int, c_void_p, c_void_p,
                                        c_int, c_void_p, c_int, c_float, c_float, c_int, c_double, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -63,6 +65,8 @@ SIGNATURES = {
     "mvp_heatmap_decode": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, P(c_int), c_int, c_void_p,
                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                    c_void_p]),
+    "mvp_heatmap_peaks": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                  c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "mvp_warp_is_separable": (c_int, [P(c_double), c_int, c_int, P(c_int)]),
     "mvp_heatmap_revert": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                    c_void_p]),

@@ -59,12 +59,16 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
                              origin_camera_idx=0, script_path=None, project_dir="", recording_length_seconds=10,
                              keep_unsynced_files=False, triangulation="reference", inlier_px=10.0,
                              min_confidence=0.0, refine=None, cov_floor=1.0, sync_from_pose=False, max_lag=60,
-                             fix_label_swaps=None):
+                             fix_label_swaps=None, max_peaks=4, peak_threshold=0.1, peak_min_rel=0.3):
     """triangulation / inlier_px / min_confidence (no reference counterpart): "reference" (default)
     triangulates from cameras [0, 1] and writes exactly the reference's files; "all_views" and
     "robust" use every camera in camera_names (estimate_pose_from_video), record the three
     settings in recording_log.yaml and also write kpts_3d_inliers.npy (T,17,V) bool and, for
-    "robust", kpts_3d_reproj_err.npy (T,17,V) f32.
+    "robust", kpts_3d_reproj_err.npy (T,17,V) f32.  "peaks" (max_peaks, peak_threshold,
+    peak_min_rel: estimate_pose_from_video's max_peaks, peak_thr, peak_min_rel) also keeps the
+    modes of every heatmap, written as kpts_2d_peaks.npy (T,17,M,3,V) f32, and lets the geometry
+    choose among them: kpts_2d_selected.npy (T,17,3,V) f32 and kpts_3d_peak_sel.npy (T,17,V) int8 are
+    written beside the "robust" files and the three settings recorded too; kpts_2d.npy stays the argmax.
     refine / cov_floor (no reference counterpart): "unit", "conf" or "heatmap" refines the
     triangulated points by maximum likelihood (get_pose_3D); kpts_3d.npy then holds the refined
     points, and kpts_3d_seed.npy, kpts_3d_cov.npy (T,17,3,3) f32 and kpts_3d_refine_status.npy
@@ -100,6 +104,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
     if triangulation != "reference":
         robust_kw = {"triangulation": triangulation, "inlier_px": inlier_px, "min_conf": min_confidence,
                      "return_info": True}
+    if triangulation == "peaks":
+        robust_kw.update({"max_peaks": max_peaks, "peak_thr": peak_threshold, "peak_min_rel": peak_min_rel})
     if refine is not None:
         robust_kw.update({"refine": refine, "cov_floor": cov_floor, "return_info": True})
     if sync_from_pose:
@@ -123,6 +129,12 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
             if info[0][key] is not None:
                 log[name] = str(os.path.join(recordings_folder, name + ".npy"))
                 extra[name] = info[0][key]
+    if triangulation == "peaks":
+        log.update({"max_peaks": int(max_peaks), "peak_threshold": float(peak_threshold),
+                    "peak_min_rel": float(peak_min_rel)})
+        for key, name in (("peaks", "kpts_2d_peaks"), ("kpts_selected", "kpts_2d_selected"), ("sel", "kpts_3d_peak_sel")):
+            log[name] = str(os.path.join(recordings_folder, name + ".npy"))
+            extra[name] = info[0][key]
     if refine is not None:
         log.update({"refine": refine, "cov_floor": float(cov_floor)})
         for key, name in (("seed", "kpts_3d_seed"), ("cov", "kpts_3d_cov"), ("refine_status", "kpts_3d_refine_status")):
@@ -158,7 +170,8 @@ def record_and_estimate_pose(camera_names, estimator_model="coco_base", detector
 def record_and_estimate_pose_parser(extensions=False):
     """Flags of record_and_estimate_pose.py:63-78; extensions=True (what the command line uses)
     adds the flags beyond the reference's: --triangulation, --inlier_px, --min_confidence,
-    --refine, --cov_floor, --sync_from_pose, --max_lag, --fix_label_swaps."""
+    --refine, --cov_floor, --sync_from_pose, --max_lag, --fix_label_swaps, --max_peaks,
+    --peak_threshold, --peak_min_rel."""
     p = argparse.ArgumentParser()
     p.add_argument("--camera_names", nargs="+", required=True, help="List of camera names")
     p.add_argument("--estimator_model")
@@ -175,9 +188,12 @@ def record_and_estimate_pose_parser(extensions=False):
     p.add_argument("--recording_length_seconds", type=int)
     p.add_argument("--keep_unsynced_files", action="store_true")
     if extensions:   # N-view triangulation (estimate_pose_from_video's `triangulation`)
-        p.add_argument("--triangulation", choices=["reference", "all_views", "robust"])
+        p.add_argument("--triangulation", choices=["reference", "all_views", "robust", "peaks"])
         p.add_argument("--inlier_px", type=float)
         p.add_argument("--min_confidence", type=float)
+        p.add_argument("--max_peaks", type=int)             # --triangulation peaks: modes kept per heatmap
+        p.add_argument("--peak_threshold", type=float)
+        p.add_argument("--peak_min_rel", type=float)
         p.add_argument("--refine", choices=["unit", "conf", "heatmap"])   # maximum-likelihood refinement
         p.add_argument("--cov_floor", type=float)
         p.add_argument("--sync_from_pose", action="store_true")   # frame offsets from the 2D keypoints

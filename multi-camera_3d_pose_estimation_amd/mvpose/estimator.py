@@ -132,7 +132,8 @@ class BatchPoseEstimator:
         return cm, rm, cs, sep
 
     def run(self, frames: torch.Tensor, n_views: int = 1, kpts_tkv: torch.Tensor | None = None,
-            argmax: bool = False, overlap_moments: bool = False, bboxes=None, bbox_thr: float | None = None):
+            argmax: bool = False, overlap_moments: bool = False, bboxes=None, bbox_thr: float | None = None,
+            max_peaks: int = 0, peak_thr: float = 0.1, peak_min_rel: float = 0.3, peak_radius: int = 1):
         """frames: (N, H, W, 3) uint8 on the GPU, ordered (t, v) when n_views > 1.
         bboxes: None (every crop = the whole image), (N, 4) host xyxy image boxes (a row of
         NaNs = no detection = the whole image), or a CUDA float32 (N, >=4) tensor such as the
@@ -142,7 +143,10 @@ class BatchPoseEstimator:
         Returns dict: keypoints (N,17,2) f32 image px, scores (N,17) f32,
         gaussians (N,17,6) f64 [mx,my,vxx,vxy,vxy,vyy], and optionally argmax.
         overlap_moments: gaussians are produced on a side stream; read them only after
-        wait_moments(out) (or a device synchronisation)."""
+        wait_moments(out) (or a device synchronisation).
+        max_peaks > 0: also "peaks" (N/n_views, 17, max_peaks, 3, n_views) f32 and "peak_counts"
+        (N/n_views, 17, n_views) int32, ops.heatmap_peaks of the flip-averaged maps with this
+        run's crop geometry (peak_thr, peak_min_rel, peak_radius: its thr, min_rel, radius)."""
         if frames.dtype != torch.uint8 or not frames.is_cuda or not frames.is_contiguous():
             raise ValueError("frames must be a contiguous uint8 CUDA tensor (N, H, W, 3)")
         n, h, w, c = frames.shape
@@ -200,6 +204,11 @@ class BatchPoseEstimator:
         out = {"keypoints": kp, "scores": sc, "gaussians": gauss, "heatmaps": avg, "moments_done": done}
         if argmax:
             out["argmax"] = am
+        if max_peaks:
+            from . import ops
+            out["peaks"], out["peak_counts"] = ops.heatmap_peaks(
+                avg, center_scale[:n], max_peaks=max_peaks, radius=peak_radius, thr=peak_thr, min_rel=peak_min_rel,
+                n_views=n_views, input_size=(INPUT_HW[1], INPUT_HW[0]))
         return out
 
     def revert_heatmaps(self, index: int = 0) -> np.ndarray:

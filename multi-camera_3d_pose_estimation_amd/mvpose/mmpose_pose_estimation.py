@@ -146,17 +146,18 @@ class PoseEstimator:
         return out
 
     def run(self, frames: torch.Tensor, n_views: int = 1, kpts_tkv: torch.Tensor | None = None,
-            overlap_moments: bool = False, argmax: bool = False, bboxes=None) -> dict:
+            overlap_moments: bool = False, argmax: bool = False, bboxes=None, **peak_kw) -> dict:
         """Batched predict on device-resident frames (N, H, W, 3) uint8 ordered (t, v): the
         detector (when enabled) and the reference's hand-off on every camera-frame, then
         BatchPoseEstimator.run with those boxes; stream-ordered, no host synchronisation on
-        the RTMDetector path.  bboxes overrides the detector."""
+        the RTMDetector path.  bboxes overrides the detector.  peak_kw: BatchPoseEstimator.run's
+        max_peaks, peak_thr, peak_min_rel, peak_radius."""
         est = self.estimator(frames.shape[1:3])
         if bboxes is None and self.detector is not None:
             bboxes = self.bboxes_for(frames)
         thr = self.bbox_thr if isinstance(bboxes, torch.Tensor) and bboxes.is_cuda else None
         return est.run(frames, n_views=n_views, kpts_tkv=kpts_tkv, overlap_moments=overlap_moments, argmax=argmax,
-                       bboxes=bboxes, bbox_thr=thr)
+                       bboxes=bboxes, bbox_thr=thr, **peak_kw)
 
     def predict_batch(self, frames, bboxes=None, overlap_moments=False):
         """frames (N, H, W, 3) uint8 (numpy or a CUDA tensor) -> BatchPoseEstimator.run's dict

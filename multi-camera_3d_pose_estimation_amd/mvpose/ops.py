@@ -21,6 +21,8 @@ TRI_ALL_VIEWS = 1
 TRI_EXACT_JACOBI = 0x10  # mode flag: exact Jacobi SVD for every point (mvpose.h)
 TRI_TOLERANCE = 0x20     # mode flag: throughput solver, certified bit-identical to the exact path (mvpose.h)
 TRI_ROBUST = 2           # Python-level only (MultiViewPipeline mode): triangulate_robust, never an mvp_triangulate mode
+TRI_PEAKS = 3            # Python-level only (MultiViewPipeline mode): heatmap_peaks + triangulate_peaks
+MAX_PEAKS = 4            # mvpose.h MVP_MAX_PEAKS
 REFINE_W_UNIT = 0        # mvp_triangulate_refine weights (mvpose.h MVP_REFINE_W_*)
 REFINE_W_CONF = 1
 REFINE_W_GAUSS = 2
@@ -194,6 +196,67 @@ def triangulate_robust(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence
     call("mvp_triangulate_robust", ptr(kpts), n, V, ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
          float(min_conf), ptr(out), ptr(bits), ptr(err), stream(kpts.device))
     return out, _unpack_view_bits(bits, nv), err
+
+
+def heatmap_peaks(heatmaps: torch.Tensor, center_scale: torch.Tensor, *, max_peaks: int = 4, radius: int = 1,
+                  thr: float = 0.1, min_rel: float = 0.3, n_views: int = 1, input_size=(192, 256)):
+    """Up to max_peaks local maxima of every heatmap, decoded like the argmax (mvp_heatmap_peaks; the
+    peak definition is stated in include/mvpose.h; no reference counterpart).
+
+    heatmaps (N, K, H, W) float32 on GPU: the maps the decode looks at (BatchPoseEstimator.run's
+    "heatmaps"), crops ordered (t, v) when n_views > 1; center_scale (N, 4) float32 (cx, cy, sw,
+    sh); input_size the network input (w, h).  A peak exceeds thr, beats its (2·radius+1)² window
+    and, after the first, reaches min_rel times the first.  Returns (peaks (N/V, K, max_peaks, 3,
+    V) float32 [x, y, score] in image pixels, best first — peaks[:, :, m] has the kpts_2d layout,
+    unfilled slots x = y = NaN, score 0 — and counts (N/V, K, V) int32)."""
+    _require(heatmaps, torch.float32, "heatmaps")
+    _require(center_scale, torch.float32, "center_scale")
+    if heatmaps.dim() != 4:
+        raise ValueError(f"heatmaps must be (N, K, H, W), got {tuple(heatmaps.shape)}")
+    N, K, H, W = heatmaps.shape
+    if tuple(center_scale.shape) != (N, 4):
+        raise ValueError(f"center_scale must be ({N}, 4), got {tuple(center_scale.shape)}")
+    M, V = int(max_peaks), int(n_views)
+    if V < 1 or N % V:
+        raise ValueError(f"n_views={V} does not divide the {N} crops")
+    if not 1 <= M <= MAX_PEAKS:
+        raise ValueError(f"max_peaks={M}: 1..{MAX_PEAKS}")
+    peaks = torch.empty((N // V, K, M, 3, V), dtype=torch.float32, device=heatmaps.device)
+    counts = torch.empty((N // V, K, V), dtype=torch.int32, device=heatmaps.device)
+    call("mvp_heatmap_peaks", ptr(heatmaps), N, K, H, W, ptr(center_scale), int(input_size[0]), int(input_size[1]),
+         M, int(radius), float(thr), float(min_rel), V, ptr(peaks), ptr(counts), stream(heatmaps.device))
+    return peaks, counts
+
+
+def triangulate_peaks(peaks: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], inlier_px: float = 10.0,
+                      min_conf: float = 0.0):
+    """triangulate_robust over several candidates per view, choosing one per inlier view
+    (mvp_triangulate_peaks; the algorithm is stated in include/mvpose.h; no reference counterpart).
+
+    peaks (..., M, 3, V) float32 on GPU (heatmap_peaks' layout: slot m of a point is a kpts
+    column set), cams and cam_idx as for triangulate_robust.  Returns (xyz (..., 3) float32,
+    inliers (..., NV) bool, sel (..., NV) int8: the slot each inlier view used, -1 otherwise,
+    err (..., NV) float32: the selected candidate's reprojection error, for a valid view outside
+    the mask its nearest candidate's, and kpts (..., 3, V) float32: slot 0 with the inlier views'
+    columns replaced by their selected candidates — a kpts_2d for every later stage).  With
+    M = 1 xyz and inliers are triangulate_robust's bit for bit and kpts is the input."""
+    _require(peaks, torch.float32, "peaks")
+    if peaks.dim() < 3 or peaks.shape[-2] != 3 or not 1 <= peaks.shape[-3] <= MAX_PEAKS:
+        raise ValueError(f"peaks must be (..., M, 3, V) with 1 <= M <= {MAX_PEAKS}, got {tuple(peaks.shape)}")
+    M = int(peaks.shape[-3])
+    V, _, _, ci = _tri_args(peaks, cams, cam_idx)
+    lead = tuple(peaks.shape[:-3])
+    n = int(np.prod(lead)) if lead else 1
+    nv = len(ci)
+    dev = peaks.device
+    out = torch.empty(lead + (3,), dtype=torch.float32, device=dev)
+    bits = torch.empty(lead, dtype=torch.uint8, device=dev)
+    sel = torch.empty(lead + (nv,), dtype=torch.int8, device=dev)
+    err = torch.empty(lead + (nv,), dtype=torch.float32, device=dev)
+    kpts = torch.empty(lead + (3, V), dtype=torch.float32, device=dev)
+    call("mvp_triangulate_peaks", ptr(peaks), n, M, V, ptr(cams), cams.shape[0], ci, nv, float(inlier_px),
+         float(min_conf), ptr(out), ptr(bits), ptr(sel), ptr(err), ptr(kpts), stream(dev))
+    return out, _unpack_view_bits(bits, nv), sel, err, kpts
 
 
 def triangulate_refine(kpts: torch.Tensor, cams: torch.Tensor, cam_idx: Sequence[int], xyz0: torch.Tensor, *,

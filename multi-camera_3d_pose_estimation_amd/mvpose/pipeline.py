@@ -9,6 +9,8 @@ process(frames (T, V, H, W, 3) uint8 on GPU) returns, device-resident:
 With refine= (no reference counterpart) kpts_3d holds the maximum-likelihood refinement of the
 triangulated points and kpts_3d_seed, kpts_3d_cov (T, 17, 3, 3), tri_refine_cost and
 tri_refine_status come with it (ops.triangulate_refine).
+With mode=ops.TRI_PEAKS (no reference counterpart) up to max_peaks modes of every heatmap are kept
+(kpts_2d_peaks) and the triangulation chooses among them (kpts_2d_selected, tri_peak_sel).
 
 process_people(frames, bboxes (T, V, P, 4)) is the same path for several people per camera (no
 reference counterpart): the 2D stage per person box, ops.associate_views across the cameras, then
@@ -34,7 +36,8 @@ class MultiViewPipeline:
     def __init__(self, camera_params, estimator: BatchPoseEstimator | None = None, camera_indices=(0, 1),
                  mode: int = ops.TRI_REFERENCE, device="cuda", detector=None, bbox_thr: float = 0.3,
                  tri_solver: str = "tolerance", inlier_px: float = 10.0, min_conf: float = 0.0,
-                 refine: str | None = None, cov_floor: float = 1.0, **estimator_kw):
+                 refine: str | None = None, cov_floor: float = 1.0, max_peaks: int = 4, peak_thr: float = 0.1,
+                 peak_min_rel: float = 0.3, peak_radius: int = 1, **estimator_kw):
         """camera_params: {camera key: [K, R, T, dist]} (utils.get_params_from_name order),
         keys 0..V-1 as the reference assumes (pose_estimation.py:276-280).
         detector: an mvpose.rtmdet.RTMDetector run on every camera-frame before the crops
@@ -48,6 +51,15 @@ class MultiViewPipeline:
         per point at inlier_px undistorted pixels, views below min_conf ignored); process() then
         also returns tri_inliers (T, 17, NV) bool and tri_reproj_err (T, 17, NV) float32.
         tri_solver does not apply in this mode.
+        mode=ops.TRI_PEAKS: up to max_peaks modes of every heatmap (ops.heatmap_peaks with
+        peak_thr, peak_min_rel, peak_radius) and ops.triangulate_peaks over camera_indices, which
+        chooses one mode per inlier view; process() leaves kpts_2d untouched (the argmax) and also
+        returns kpts_2d_peaks (T, 17, M, 3, V), kpts_2d_selected (T, 17, 3, V: kpts_2d with the
+        inlier views' columns replaced by the chosen modes — the kpts_2d for every later stage),
+        tri_inliers, tri_reproj_err and tri_peak_sel (T, 17, NV) int8.  refine "unit" / "conf" then
+        run on kpts_2d_selected over the inliers; "heatmap" raises ValueError (the Gaussian moments
+        are those of the whole, possibly bimodal map, not of the chosen mode).  tri_solver does
+        not apply.  process_people is unchanged.
         refine: None (default: process() as without it) or "unit" / "conf" / "heatmap": the mode's
         points seed ops.triangulate_refine over camera_indices (TRI_ROBUST: over each point's
         inliers); "heatmap" weighs each view by its own heatmaps_2d Gaussian + cov_floor px².
@@ -59,8 +71,16 @@ class MultiViewPipeline:
         self.cov_floor = float(cov_floor)
         if tri_solver not in ("tolerance", "reference_compat"):
             raise ValueError(f"tri_solver {tri_solver!r}: 'tolerance' or 'reference_compat'")
-        if mode == ops.TRI_ROBUST and tri_solver != "tolerance":
-            raise ValueError("tri_solver does not apply to mode=ops.TRI_ROBUST: leave it at its default")
+        if mode in (ops.TRI_ROBUST, ops.TRI_PEAKS) and tri_solver != "tolerance":
+            raise ValueError("tri_solver does not apply to mode=ops.TRI_ROBUST / TRI_PEAKS: leave it at its default")
+        if mode == ops.TRI_PEAKS:
+            if refine == "heatmap":
+                raise ValueError('refine="heatmap" does not apply to mode=ops.TRI_PEAKS: the heatmap moments describe '
+                                 "the whole, possibly bimodal map, not the selected mode")
+            if not 1 <= int(max_peaks) <= ops.MAX_PEAKS:
+                raise ValueError(f"max_peaks={max_peaks}: 1..{ops.MAX_PEAKS}")
+        self.peak_kw = {"max_peaks": int(max_peaks), "peak_thr": float(peak_thr), "peak_min_rel": float(peak_min_rel),
+                        "peak_radius": int(peak_radius)}
         self.tri_solver = tri_solver
         self.inlier_px = float(inlier_px)
         self.min_conf = float(min_conf)
@@ -99,7 +119,7 @@ class MultiViewPipeline:
         else:
             bb = None if bboxes is None else np.asarray(bboxes, np.float64).reshape(T * V, 4)
         r = self.estimator.run(flat, n_views=V, kpts_tkv=out["kpts_2d"], overlap_moments=overlap_moments, bboxes=bb,
-                               bbox_thr=thr)
+                               bbox_thr=thr, **(self.peak_kw if self.mode == ops.TRI_PEAKS else {}))
         out["heatmaps_2d"] = r["gaussians"].reshape(T, V, N_JOINTS, 6)
         if r["moments_done"] is not None:
             out["moments_done"] = r["moments_done"]
@@ -109,20 +129,29 @@ class MultiViewPipeline:
             out["kpts_3d"], out["tri_inliers"], out["tri_reproj_err"] = ops.triangulate_robust(
                 out["kpts_2d"], self.cams, self.camera_indices, inlier_px=self.inlier_px, min_conf=self.min_conf)
             return self._refine(out, out["tri_inliers"]) if self.refine is not None else out
+        if self.mode == ops.TRI_PEAKS:
+            out["kpts_2d_peaks"] = r["peaks"]
+            (out["kpts_3d"], out["tri_inliers"], out["tri_peak_sel"], out["tri_reproj_err"],
+             out["kpts_2d_selected"]) = ops.triangulate_peaks(r["peaks"], self.cams, self.camera_indices,
+                                                              inlier_px=self.inlier_px, min_conf=self.min_conf)
+            if self.refine is not None:
+                return self._refine(out, out["tri_inliers"], kpts=out["kpts_2d_selected"])
+            return out
         if self.refine is not None:
             out.pop("kpts_3d", None)       # the previous call's refined points are not a seed buffer
         out["kpts_3d"] = ops.triangulate(out["kpts_2d"], self.cams, self.camera_indices, mode=self.mode,
                                          out=out.get("kpts_3d"), tolerance=self.tri_solver == "tolerance")
         return self._refine(out, None) if self.refine is not None else out
 
-    def _refine(self, out: dict, mask) -> dict:
+    def _refine(self, out: dict, mask, kpts=None) -> dict:
         if self.refine == "heatmap":
             self.wait(out)                 # overlap_moments: the side stream's heatmaps_2d before they are read
         out["kpts_3d_seed"] = out["kpts_3d"]
         out["kpts_3d"], out["kpts_3d_cov"], out["tri_refine_cost"], out["tri_refine_status"] = ops.triangulate_refine(
-            out["kpts_2d"], self.cams, self.camera_indices, out["kpts_3d_seed"], weights=self.refine,
-            gauss=out["heatmaps_2d"] if self.refine == "heatmap" else None, mask=mask,
-            min_conf=self.min_conf if self.mode == ops.TRI_ROBUST else 0.0, cov_floor=self.cov_floor)
+            out["kpts_2d"] if kpts is None else kpts, self.cams, self.camera_indices, out["kpts_3d_seed"],
+            weights=self.refine, gauss=out["heatmaps_2d"] if self.refine == "heatmap" else None, mask=mask,
+            min_conf=self.min_conf if self.mode in (ops.TRI_ROBUST, ops.TRI_PEAKS) else 0.0,
+            cov_floor=self.cov_floor)
         return out
 
     def detect(self, flat: torch.Tensor) -> torch.Tensor:

@@ -33,7 +33,7 @@ from .estimator import BatchPoseEstimator
 from .hrnet import N_JOINTS
 
 
-TRIANGULATION_METHODS = ("reference", "all_views", "robust")
+TRIANGULATION_METHODS = ("reference", "all_views", "robust", "peaks")
 REFINE_MODES = (None, "unit", "conf", "heatmap")
 SYNC_MODES = (None, "pose")
 
@@ -45,7 +45,7 @@ def _check_refine(refine):
 
 def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices=None,
                 ignore_nonlinear_distortions=False, device=None, method="reference", inlier_px=10.0,
-                min_conf=0.0, return_info=False, refine=None, heatmaps_2d=None, cov_floor=1.0):
+                min_conf=0.0, return_info=False, refine=None, heatmaps_2d=None, cov_floor=1.0, peaks=None):
     """camera_params {key: [K, R, T, dist]} (get_params_from_name order), all_kpts_2d
     (T, J, 3, V) -> (T, J, 3) float32 numpy (float64 if world_trans_rot is given).
 
@@ -55,7 +55,13 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     cameras with per-point outlier-view rejection at inlier_px undistorted pixels, views below
     min_conf ignored).  return_info: also return {"inliers": (T, J, NV) bool — the listed
     views that entered each point's solve (None for "reference": the selection is internal),
-    "reproj_err": (T, J, NV) float32 (method "robust" only, else None)}.
+    "reproj_err": (T, J, NV) float32 (methods "robust" and "peaks", else None)}.
+    method "peaks" (ops.triangulate_peaks) reads peaks (T, J, M, 3, V), the modes of every heatmap
+    (get_pose_2D / run_pose_est with max_peaks), instead of all_kpts_2d and chooses one per inlier
+    view; info then also holds "sel" (T, J, NV) int8, the slot each inlier view used, and
+    "kpts_selected" (T, J, 3, V), slot 0 with the inlier views' columns replaced by the chosen
+    modes.  refine then runs on kpts_selected over the inliers ("heatmap" raises ValueError: the
+    Gaussians describe the whole map, not the chosen mode).
 
     refine: None (default) or "unit" / "conf" / "heatmap": the chosen method's points seed
     ops.triangulate_refine (maximum-likelihood refinement over the listed cameras, for "robust"
@@ -67,6 +73,12 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     if method not in TRIANGULATION_METHODS:
         raise ValueError(f"method {method!r}: one of {TRIANGULATION_METHODS}")
     _check_refine(refine)
+    if method == "peaks":
+        if peaks is None:
+            raise ValueError('method="peaks" needs peaks, the (T, J, M, 3, V) heatmap modes')
+        if refine == "heatmap":
+            raise ValueError('refine="heatmap" does not apply to method="peaks": the heatmap Gaussians describe the '
+                             "whole map, not the selected mode")
     if refine == "heatmap" and heatmaps_2d is None:
         raise ValueError('refine="heatmap" needs heatmaps_2d, the (T, V, J, 6) heatmap Gaussians')
     dev = torch.device(device if device is not None else "cuda")
@@ -89,6 +101,13 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
         out = xyz.cpu().numpy()
         info["inliers"] = inliers.cpu().numpy()
         info["reproj_err"] = err.cpu().numpy() if err is not None else None
+    elif method == "peaks":
+        pk = torch.as_tensor(np.ascontiguousarray(np.asarray(peaks, dtype=np.float32)), device=dev)
+        xyz, inliers, sel, err, kp = ops.triangulate_peaks(pk, cams, positions, inlier_px=inlier_px, min_conf=min_conf)
+        seed_dev, mask_dev = xyz, inliers
+        out = xyz.cpu().numpy()
+        info.update({"inliers": inliers.cpu().numpy(), "reproj_err": err.cpu().numpy(), "sel": sel.cpu().numpy(),
+                     "kpts_selected": kp.cpu().numpy()})
     elif method == "all_views":
         seed_dev = ops.triangulate(kp, cams, positions, mode=ops.TRI_ALL_VIEWS)
         out = seed_dev.cpu().numpy()
@@ -102,7 +121,7 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
             gauss = torch.as_tensor(np.ascontiguousarray(np.asarray(heatmaps_2d, dtype=np.float64)), device=dev)
         xyz, cov, cost, status = ops.triangulate_refine(
             kp, cams, positions, seed_dev, weights=refine, gauss=gauss, mask=mask_dev,
-            min_conf=min_conf if method == "robust" else 0.0, cov_floor=cov_floor)
+            min_conf=min_conf if method in ("robust", "peaks") else 0.0, cov_floor=cov_floor)
         info.update({"seed": out, "cov": cov.cpu().numpy(), "refine_cost": cost.cpu().numpy(),
                      "refine_status": status.cpu().numpy()})
         out = xyz.cpu().numpy()
@@ -116,7 +135,8 @@ def get_pose_3D(camera_params, all_kpts_2d, world_trans_rot=None, camera_indices
     return (out, info) if return_info else out
 
 
-def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17)):
+def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17), max_peaks=0, peak_thr=0.1,
+                peak_min_rel=0.3, peak_radius=1):
     """pose_estimation.py:71-151.  frames: V frames (H, W, 3) uint8 of one time step.
 
     model: a BatchPoseEstimator / mvpose PoseEstimator or one's bound predict (the V frames
@@ -126,11 +146,17 @@ def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17)):
     Returns (results_stacked (17, 3, V) float32, heatmaps list of V arrays).
     confidence and pose_keypoints select only the keypoints the reference DRAWS on the
     frames (:117-131, then discarded with the GUI window), so they do not change the
-    output — as in the reference."""
+    output — as in the reference.
+    max_peaks > 0 (a GPU estimator only): a third result, peaks (17, max_peaks, 3, V) float32, the
+    modes of every heatmap (ops.heatmap_peaks with peak_thr, peak_min_rel, peak_radius)."""
     est = resolve_estimator(model)
+    if max_peaks and est is None:
+        raise ValueError("max_peaks needs a BatchPoseEstimator / PoseEstimator: a per-frame callable returns no heatmaps")
     if est is not None:
         batch = np.ascontiguousarray(np.stack([np.asarray(f) for f in frames]))
-        r = est.run(torch.from_numpy(batch).to(est.device).contiguous())
+        kw = {} if not max_peaks else {"n_views": len(batch), "max_peaks": int(max_peaks), "peak_thr": peak_thr,
+                                       "peak_min_rel": peak_min_rel, "peak_radius": peak_radius}
+        r = est.run(torch.from_numpy(batch).to(est.device).contiguous(), **kw)
         pts = r["keypoints"].cpu().numpy()
         conf = r["scores"].cpu().numpy()
         heat = list(r["gaussians"].cpu().numpy())
@@ -147,6 +173,8 @@ def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17)):
         except (IndexError, KeyError, TypeError):
             heat = []
     stacked = np.stack([np.concatenate((p, np.expand_dims(c, 1)), axis=1) for p, c in zip(pts, conf)], axis=2)
+    if max_peaks:
+        return stacked, heat, r["peaks"][0].cpu().numpy()
     return stacked, heat
 
 
@@ -271,14 +299,18 @@ class FrameStreamer:
         for _ in self.pool.map(cp, jobs):
             pass
 
-    def run(self, stacks, n_frames=None):
+    def run(self, stacks, n_frames=None, **peak_kw):
         """stacks: V arrays (T, H, W, 3) uint8 (memory-mapped .npy or in memory).  Returns
-        device tensors kpts_2d (T, 17, 3, V) f32 and heatmaps (T, V, 17, 6) f64."""
+        device tensors kpts_2d (T, 17, 3, V) f32 and heatmaps (T, V, 17, 6) f64; with peak_kw
+        (BatchPoseEstimator.run's max_peaks > 0, peak_thr, peak_min_rel, peak_radius) also peaks
+        (T, 17, max_peaks, 3, V) f32."""
         from concurrent.futures import ThreadPoolExecutor
         T = min(len(s) for s in stacks) if n_frames is None else int(n_frames)
         dev = self.device
         kp = torch.empty((T, N_JOINTS, 3, self.V), dtype=torch.float32, device=dev)
         hm = torch.empty((T, self.V, N_JOINTS, 6), dtype=torch.float64, device=dev)
+        M = int(peak_kw.get("max_peaks", 0))
+        pk = torch.empty((T, N_JOINTS, M, 3, self.V), dtype=torch.float32, device=dev) if M else None
         chunks = [(t, min(T, t + self.step)) for t in range(0, T, self.step)]
         main = torch.cuda.current_stream(dev)
         if any(isinstance(s, torch.Tensor) and s.is_cuda for s in stacks):
@@ -291,9 +323,12 @@ class FrameStreamer:
                 fr = self.dev[0][:n]
                 for v, s in enumerate(dstacks):
                     fr[:, v].copy_(s[t0:t1])
-                r = self.est.run(fr.reshape(n * self.V, self.H, self.W, 3), n_views=self.V, kpts_tkv=kp[t0:t1])
+                r = self.est.run(fr.reshape(n * self.V, self.H, self.W, 3), n_views=self.V, kpts_tkv=kp[t0:t1],
+                                 **peak_kw)
                 hm[t0:t1] = r["gaussians"].reshape(n, self.V, N_JOINTS, 6)
-            return kp, hm
+                if M:
+                    pk[t0:t1] = r["peaks"]
+            return (kp, hm, pk) if M else (kp, hm)
         with ThreadPoolExecutor(max_workers=1) as pool:
             fut = pool.submit(self._gather, stacks, *chunks[0], 0) if chunks else None
             for i, (t0, t1) in enumerate(chunks):
@@ -314,16 +349,19 @@ class FrameStreamer:
                     self.copied[k] = ev
                 main.wait_event(ev)
                 fr = self.dev[k][:n].reshape(n * self.V, self.H, self.W, 3)
-                r = self.est.run(fr, n_views=self.V, kpts_tkv=kp[t0:t1])
+                r = self.est.run(fr, n_views=self.V, kpts_tkv=kp[t0:t1], **peak_kw)
                 hm[t0:t1] = r["gaussians"].reshape(n, self.V, N_JOINTS, 6)
+                if M:
+                    pk[t0:t1] = r["peaks"]
                 ce = torch.cuda.Event()
                 ce.record(main)
                 self.consumed[k] = ce
-        return kp, hm
+        return (kp, hm, pk) if M else (kp, hm)
 
 
 def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=None, start_end_frames=(0, -1),
-                 frame_shape=(1080, 1920), batch_frames=128):
+                 frame_shape=(1080, 1920), batch_frames=128, max_peaks=0, peak_thr=0.1, peak_min_rel=0.3,
+                 peak_radius=1):
     """pose_estimation.py:157-244 -> kpts_2d (T, 17, 3, V) float32, heatmaps (T, V, 17, 6)
     float64 (numpy).  recording_paths values may also be in-memory (T, H, W, 3) uint8 arrays.
 
@@ -331,7 +369,9 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
     every frame through the batched GPU path (FrameStreamer); a model name -> build_estimator;
     any other per-frame callable with the reference's contract -> get_pose_2D frame by frame,
     as the reference loops (:184-190).  confidence does not change the output (it only
-    selects what the reference draws, :117-131)."""
+    selects what the reference draws, :117-131).
+    max_peaks > 0 (GPU estimators only): a third result, peaks (T, 17, max_peaks, 3, V) float32, the
+    modes of every heatmap (ops.heatmap_peaks with peak_thr, peak_min_rel, peak_radius)."""
     gpu_model = isinstance(model, str) or resolve_estimator(model) is not None
     frames = load_frames(recording_paths, start_end_frames, device=video_device() if gpu_model else None)
     cams = list(frames.keys()) if camera_indices is None else list(camera_indices)
@@ -339,29 +379,41 @@ def run_pose_est(model, confidence=0.5, camera_indices=None, recording_paths=Non
     V = len(stacks)
     H, W = stacks[0].shape[1:3]
     est = build_estimator(model, frame_hw=(H, W)) if isinstance(model, str) else resolve_estimator(model)
+    if est is None and max_peaks:
+        raise ValueError("max_peaks needs a BatchPoseEstimator / PoseEstimator: a per-frame callable returns no heatmaps")
     if est is None:                                   # a generic per-frame callable
         stacks = [s.cpu().numpy() if isinstance(s, torch.Tensor) else s for s in stacks]
         T = min(len(s) for s in stacks)
         res = [get_pose_2D([s[t] for s in stacks], model, confidence) for t in range(T)]
         return (np.array([r[0] for r in res], dtype=np.float32).reshape(T, N_JOINTS, 3, V),
                 np.array([r[1] for r in res]))
+    peak_kw = {} if not max_peaks else {"max_peaks": int(max_peaks), "peak_thr": peak_thr, "peak_min_rel": peak_min_rel,
+                                        "peak_radius": peak_radius}
     with FrameStreamer(est, V, (H, W), batch_frames) as fs:
-        kp, hm = fs.run(stacks)
-    return kp.cpu().numpy(), hm.cpu().numpy()
+        res = fs.run(stacks, **peak_kw)
+    return tuple(a.cpu().numpy() for a in res)
 
 
 def estimate_pose_from_video(camera_names, recording_paths, model, detector_model="coco_base", model_yaml="",
                              start_end_frames=(0, -1), confidence=0, extrinsic_params_dir="",
                              recompute_kpts_2d=True, triangulation="reference", inlier_px=10.0, min_conf=0.0,
                              return_info=False, refine=None, cov_floor=1.0, sync=None, max_lag=60,
-                             fix_swaps=None):
+                             fix_swaps=None, max_peaks=4, peak_thr=0.1, peak_min_rel=0.3, peak_radius=1):
     """pose_estimation.py:259-327.  recompute_kpts_2d replaces the reference's interactive
     y/n prompt when kpts_2d.npy already exists (:287-289).
 
     triangulation: "reference" (default) triangulates from cameras [0, 1] as the reference
     hard-codes (:319); "all_views" and "robust" (get_pose_3D's methods, with inlier_px and
     min_conf) list every camera in camera_names.  return_info appends get_pose_3D's info
-    dict to the returned tuple.  refine / cov_floor: get_pose_3D's maximum-likelihood refinement
+    dict to the returned tuple.  "peaks" (every camera too) also keeps up to max_peaks modes of
+    every heatmap (peak_thr, peak_min_rel, peak_radius: ops.heatmap_peaks) and lets
+    ops.triangulate_peaks choose among them; the modes are saved beside kpts_2d.npy as
+    kpts_2d_peaks.npy (T, 17, M, 3, V), loaded from there when the 2D stage does not run, and take
+    the same per-camera frame offsets as kpts_2d; info holds them as "peaks", with get_pose_3D's
+    "sel" and "kpts_selected".  Unlike kpts_2d.npy, which the caller writes, kpts_2d_peaks.npy is
+    written here, as the 2D stage returns it (before any frame offsets); the command line then
+    writes the returned, aligned peaks over it, as it does for kpts_2d.npy.  "peaks" with fix_swaps raises ValueError (the peak lists are not
+    carried through the exchange).  refine / cov_floor: get_pose_3D's maximum-likelihood refinement
     of the triangulated points ("heatmap" reads this run's heatmaps_2d, so it needs the 2D stage
     to run: recompute_kpts_2d, or no kpts_2d.npy yet).
 
@@ -385,6 +437,12 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
         raise ValueError(f"sync {sync!r}: one of {SYNC_MODES}")
     if fix_swaps is not None and fix_swaps not in label_swaps.PRESETS:
         raise ValueError(f"fix_swaps {fix_swaps!r}: None or one of {tuple(label_swaps.PRESETS)}")
+    with_peaks = triangulation == "peaks"
+    if with_peaks and fix_swaps is not None:
+        raise ValueError('fix_swaps does not apply to triangulation="peaks": the peak lists are not carried through '
+                         "the label exchange")
+    if with_peaks and refine == "heatmap":
+        raise ValueError('refine="heatmap" does not apply to triangulation="peaks"')
     index_name, _origin = geometry.load_camera_names(extrinsic_params_dir)
     name_index = {v: k for k, v in index_name.items()}
     camera_indices = [name_index[n] for n in camera_names]
@@ -393,9 +451,15 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
         _, camera_params[i] = geometry.get_params_from_name(name, extrinsic_params_dir=extrinsic_params_dir)
     folder = os.path.dirname(recording_paths[0])
     existing = os.path.join(folder, "kpts_2d.npy")
-    heatmaps = None
+    existing_peaks = os.path.join(folder, "kpts_2d_peaks.npy")
+    heatmaps = peaks = None
     if os.path.exists(existing) and not recompute_kpts_2d:
         kpts_2d = np.load(existing)
+        if with_peaks:
+            if not os.path.exists(existing_peaks):
+                raise FileNotFoundError(f'triangulation="peaks" needs {existing_peaks} beside kpts_2d.npy: run the 2D '
+                                        "stage again (recompute_kpts_2d=True)")
+            peaks = np.load(existing_peaks)
     else:
         paths = {i: recording_paths[i] for i in camera_indices}   # as :281 indexes them
         gpu_model = isinstance(model, str) or resolve_estimator(model) is not None
@@ -404,8 +468,13 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
         if isinstance(model, str):                             # :290-297: detector + pose model from the yaml
             model = build_estimator(model, detector_model, model_yaml,
                                     frame_hw=tuple(frames[camera_indices[0]].shape[1:3]))
-        kpts_2d, heatmaps = run_pose_est(model, confidence=confidence, camera_indices=camera_indices,
-                                         recording_paths=frames, start_end_frames=(0, None))
+        res = run_pose_est(model, confidence=confidence, camera_indices=camera_indices, recording_paths=frames,
+                           start_end_frames=(0, None), max_peaks=max_peaks if with_peaks else 0, peak_thr=peak_thr,
+                           peak_min_rel=peak_min_rel, peak_radius=peak_radius)
+        kpts_2d, heatmaps = res[:2]
+        if with_peaks:
+            peaks = res[2]
+            np.save(existing_peaks, peaks)
     sync_info = {}
     if sync == "pose":
         offsets, pair_info = frame_sync.estimate_frame_offsets(kpts_2d, camera_params, max_lag=max_lag)
@@ -414,7 +483,8 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
             why = [f"{camera_names[a]}-{camera_names[b]}: {r}"
                    for (a, b), r in zip(pair_info["pairs"], pair_info["reason"]) if r]
             raise ValueError(f"sync='pose': no frame offset for camera(s) {lost} (rejected pairs: {why})")
-        (kpts_2d, heatmaps), first = frame_sync.apply_frame_offsets([kpts_2d, heatmaps], offsets, (3, 1))
+        (kpts_2d, heatmaps, peaks), first = frame_sync.apply_frame_offsets([kpts_2d, heatmaps, peaks], offsets,
+                                                                            (3, 1, 4))
         sync_info = {"frame_offsets": offsets, "frame_first": first, "sync_pairs": pair_info}
     if fix_swaps is not None:
         kpts_2d, heatmaps, swap = label_swaps.fix_label_swaps(kpts_2d, camera_params, units=fix_swaps,
@@ -428,7 +498,9 @@ def estimate_pose_from_video(camera_names, recording_paths, model, detector_mode
         listed = [0, 1] if triangulation == "reference" else list(range(len(camera_names)))
         kpts_3d, info = get_pose_3D(camera_params, kpts_2d, camera_indices=listed, method=triangulation,
                                     inlier_px=inlier_px, min_conf=min_conf, return_info=True, refine=refine,
-                                    heatmaps_2d=heatmaps, cov_floor=cov_floor)
+                                    heatmaps_2d=heatmaps, cov_floor=cov_floor, peaks=peaks)
+        if with_peaks:
+            info["peaks"] = peaks
     info.update(sync_info)
     if return_info:
         return kpts_2d, heatmaps, kpts_3d, info
