@@ -588,6 +588,9 @@ struct Decoder {
     }
 
     void video_packet_header(Bits& b) {
+        // the stuffing is its '0' and then '1's up to the byte boundary: a whole byte (0x7f) when
+        // the macroblock before it ended on one, which align() alone would not step over
+        b.skip(1);
         b.align();
         b.skip(17 + (vop_type == 1 ? fcode - 1 : 0));
         int nbits = 0;
@@ -657,21 +660,32 @@ struct Decoder {
         *dcp(n) = level;
     }
 
-    // ff_mpeg4_pred_ac on the quantised block (raster), then store the first row / column
+    // ff_mpeg4_pred_ac on the quantised block (raster), then store the first row / column.  A
+    // prediction block in a macroblock outside the picture or before the current video packet's
+    // first macroblock predicts AC values of zero (ISO/IEC 14496-2 7.4.3.3; FFmpeg clears its AC
+    // arrays at each packet start): the arrays still hold the previous packet's values there.
     void pred_ac(int n, int dir, bool ac_pred, int16_t* blk) {
         int16_t* a = acp(n);
         if (ac_pred) {
+            const int start = resync_y * mb_w + resync_x, here = mb_y * mb_w + mb_x;
             if (dir == 0) {
-                const int16_t* l = a - 16;
-                const int ql = mbq[qidx(mb_x - 1, mb_y)];
-                const bool same = mb_x == 0 || qscale == ql || n == 1 || n == 3;
-                for (int i = 1; i < 8; i++)
-                    blk[i * 8] = (int16_t)(blk[i * 8] + (same ? l[i] : rdiv(l[i] * ql, qscale)));
+                const bool own = n == 1 || n == 3;  // the left block lies in this macroblock
+                if (own || (mb_x > 0 && here - 1 >= start)) {
+                    const int16_t* l = a - 16;
+                    const int ql = mbq[qidx(mb_x - 1, mb_y)];
+                    const bool same = own || qscale == ql;
+                    for (int i = 1; i < 8; i++)
+                        blk[i * 8] = (int16_t)(blk[i * 8] + (same ? l[i] : rdiv(l[i] * ql, qscale)));
+                }
             } else {
-                const int16_t* t = a - 16 * wrap(n);
-                const int qt = mbq[qidx(mb_x, mb_y - 1)];
-                const bool same = mb_y == 0 || qscale == qt || n == 2 || n == 3;
-                for (int i = 1; i < 8; i++) blk[i] = (int16_t)(blk[i] + (same ? t[8 + i] : rdiv(t[8 + i] * qt, qscale)));
+                const bool own = n == 2 || n == 3;  // the block above lies in this macroblock
+                if (own || (mb_y > 0 && here - mb_w >= start)) {
+                    const int16_t* t = a - 16 * wrap(n);
+                    const int qt = mbq[qidx(mb_x, mb_y - 1)];
+                    const bool same = own || qscale == qt;
+                    for (int i = 1; i < 8; i++)
+                        blk[i] = (int16_t)(blk[i] + (same ? t[8 + i] : rdiv(t[8 + i] * qt, qscale)));
+                }
             }
         }
         for (int i = 1; i < 8; i++) {

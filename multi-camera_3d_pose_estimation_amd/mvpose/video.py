@@ -402,7 +402,9 @@ def decode_mp4v_device(config: bytes, samples, start=0, end=None, threads=None, 
     one 32-B record per macroblock + the non-zero inverse-quantised coefficients, ~5-10 % of a
     BGR frame's bytes), copied to the device in one transfer, and reconstructed there by one
     mvp_mp4v_reconstruct launch per GOP position: every GOP is an independent slot with its own
-    two pictures, so a launch runs one VOP of every GOP.  timings: filled with the host phases'
+    two pictures, so a launch runs one VOP of every GOP.  stream: the stream the work is queued
+    on (default: the current one); the current stream waits for it before this returns, so the
+    result may be read there without further synchronisation.  timings: filled with the host phases'
     seconds (parse, pack, launch; the launches are asynchronous)."""
     import time
     import torch
@@ -416,7 +418,13 @@ def decode_mp4v_device(config: bytes, samples, start=0, end=None, threads=None, 
     H, W, n_mb = probe.height, probe.width, probe.n_mb
     probe.close()
     dev = torch.device(device)
-    out = torch.empty((max(hi - lo, 0), H, W, 3), dtype=torch.uint8, device=dev)
+    caller = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else caller
+    # the launches on `s` write `out`: allocate it there (the caching allocator may hand back a
+    # block whose last use is still queued on the stream it was freed on) and, before returning,
+    # make the caller's current stream wait for `s`
+    with torch.cuda.stream(s):
+        out = torch.empty((max(hi - lo, 0), H, W, 3), dtype=torch.uint8, device=dev)
     if hi <= lo:
         return out
     starts = [i for i in range(hi) if i == 0 or vop_coding_type(samples[i]) == 0]
@@ -425,7 +433,6 @@ def decode_mp4v_device(config: bytes, samples, start=0, end=None, threads=None, 
     n_s = sum(b - a for a, b in gops)
     gop_base = np.concatenate([[0], np.cumsum([b - a for a, b in gops])]).astype(np.int64)
     rb = n_mb * MB_REC_BYTES
-    s = stream if stream is not None else torch.cuda.current_stream(dev)
     # records straight into one pinned buffer (torch caches pinned blocks across calls); each
     # GOP's records and coefficients go to the device on a copy stream as soon as it is parsed,
     # under the other GOPs' parsing
@@ -523,6 +530,9 @@ def decode_mp4v_device(config: bytes, samples, start=0, end=None, threads=None, 
         for k in range(steps):
             _lib.call("mvp_mp4v_reconstruct", jobs_d.data_ptr() + int(first[k]) * JOB_DTYPE.itemsize, int(n_jobs[k]),
                       W, H, s.cuda_stream)
+    if s != caller:
+        caller.wait_stream(s)
+        out.record_stream(caller)                         # allocated on s, read by the caller's stream
     if timings is not None:
         t_end = time.perf_counter()
         timings.update(parse=t_pack - t_parse, pack=t_launch - t_pack, launch=t_end - t_launch,

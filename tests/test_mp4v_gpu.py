@@ -3,7 +3,9 @@ reconstruction (mvp_mp4v_reconstruct, csrc/mp4v_recon.hip) — returns, on the d
 BGR frames the host decoder (mvp_mp4v_decode) writes: every frame, every slice, every container
 (MP4 / AVI / raw), mixed macroblock types (1MV, 4MV, skip, intra-in-P), a not-coded VOP, sizes
 that are not multiples of 16 with vectors past the picture edge, MPEG quantisation, GOPs of
-different lengths decoded as parallel slots.  Replaces cv.VideoCapture's decode of the
+different lengths decoded as parallel slots, and the rarer paths of tests/test_mp4v_paths.py
+(video packets with lost macroblocks, the intra DC through the AC VLC, saturated and 384-entry
+macroblocks, frames of one macroblock and less).  Replaces cv.VideoCapture's decode of the
 reference's mp4v recordings (utils.py:849-909; synchronize_videos.py:64,240); parity against
 cv2 / FFmpeg is unpinned (neither exists in this image)."""
 import numpy as np
@@ -92,3 +94,61 @@ def test_read_recording_device_containers(video, tmp_path):
         got = video.read_recording(p, 0, -1, device="cuda")
         assert isinstance(got, torch.Tensor) and got.is_cuda
         np.testing.assert_array_equal(got.cpu().numpy(), host[:-1], err_msg=str(p))
+
+
+# ------------------------------------------------------------------ the paths of tests/test_mp4v_paths.py
+import test_mp4v_paths as P  # noqa: E402  (the CPU builders, shared)
+
+PATH_STREAMS = {
+    "mpeg_custom": lambda n_p, seed: P.mpeg_gop(n_p, seed, "custom"),     # quant_type 1, loaded matrices, saturation
+    "packets_lost": P.packet_gop,                                        # video packets, MB_LOST in coded VOPs
+    "dc_switch": P.dc_switch_gop,                                        # intra DC through the AC VLC (mask bit 0)
+    "magnitudes": P.magnitude_gop,                                       # -2048 / 2047 entries, 384 per MB, clip8
+    "one_macroblock": P.tiny_gop,                                        # 16 x 16: a one-block grid
+    "vol_8x8": lambda n_p, seed: P.tiny_gop(n_p, seed, vol_wh=(8, 8)),   # the frame is a corner of one macroblock
+}
+
+
+def _concat(gops):
+    assert all(g.cfg == gops[0].cfg for g in gops)
+    return gops[0].cfg, [s for g in gops for s in g.samples], gops[0].w, gops[0].h
+
+
+@pytest.mark.parametrize("name", list(PATH_STREAMS))
+def test_device_equals_host_on_the_rarer_paths(video, name):
+    """Three GOPs of different lengths (4, 2 and 3 VOPs: a launch mixes intra, inter, lost and
+    absent jobs across the slots), each in a fresh slot on the device and a fresh decoder on the
+    host (decode_mp4v), whole and as an interior slice."""
+    cfg, samples, w, h = _concat([PATH_STREAMS[name](n_p, 300 + n_p) for n_p in (3, 1, 2)])
+    host = video.decode_mp4v(cfg, samples, 0, None, threads=1)
+    assert host.shape == (9, h, w, 3)
+    for sl in [(0, None), (2, 7)]:
+        got = video.decode_mp4v_device(cfg, samples, *sl, threads=3)
+        np.testing.assert_array_equal(got.cpu().numpy(), host[slice(*sl)], err_msg=f"slice {sl}")
+
+
+def test_device_dense_gop_stitches_coefficient_chunks(video):
+    """Every macroblock of every VOP holds 384 entries: mvp_mp4v_parse_many returns before the
+    GOP's end (asserted on its `done`), so decode_mp4v_device stitches several chunks per GOP."""
+    dense = [P.dense_gop(3, 95), P.dense_gop(1, 96)]
+    done, _ = P.parse_many_done(dense[0])
+    assert 1 <= done < len(dense[0].samples)
+    cfg, samples, w, h = _concat(dense)
+    host = video.decode_mp4v(cfg, samples, 0, None, threads=1)
+    for sl in [(0, None), (1, 5)]:
+        got = video.decode_mp4v_device(cfg, samples, *sl, threads=2)
+        np.testing.assert_array_equal(got.cpu().numpy(), host[slice(*sl)], err_msg=f"slice {sl}")
+
+
+def test_device_decode_on_a_side_stream_orders_the_caller(video):
+    """decode_mp4v_device(stream=side) returns a tensor the caller's current stream may read at
+    once: it is allocated on `side` and the current stream waits for `side` before the call
+    returns.  The copy back below runs on the current stream and waits for that stream alone (no
+    device-wide synchronize).  The defect this guards against was a race (output allocated on one
+    stream, written on another, nothing ordering the two), so this test cannot be relied on to
+    fail without the fix: it pins the path, not the bug."""
+    st = P.packet_gop(3, 310)
+    host = video.decode_mp4v(st.cfg, st.samples, 0, None, threads=1)
+    side = torch.cuda.Stream()
+    got = video.decode_mp4v_device(st.cfg, st.samples, stream=side)
+    np.testing.assert_array_equal(got.cpu().numpy(), host)

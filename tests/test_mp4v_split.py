@@ -5,7 +5,8 @@ simple IDCT from tests/mp4v_writer.py, half-pel prediction with per-pixel edge c
 host decoder's buffer swap) rebuilds, from the records alone, exactly the I420 pictures the
 host decoder (mvp_mp4v_decode) outputs.  Streams: I + 1MV P-VOPs, 4MV / skip / intra-in-P
 macroblocks, a not-coded VOP, frame sizes that are not multiples of 16 (vectors pointing past
-the visible edge), MPEG quantisation.  tests/test_mp4v_gpu.py holds the device kernel to the
+the visible edge), MPEG quantisation; tests/test_mp4v_paths.py adds lost macroblocks (kind 3) and
+the rest of the rarer syntax.  tests/test_mp4v_gpu.py holds the device kernel to the
 host frames; the reference's own decoder (cv2 / FFmpeg) is absent: parity vs it is unpinned."""
 import numpy as np
 import pytest
