@@ -1381,6 +1381,88 @@ int mvp_mp4v_reconstruct(const void* jobs_dev, int n_jobs, int width, int height
 int mvp_mp4v_parse_many(void* handle, int n, const uint8_t* const* data, const size_t* bytes, void* rec_out,
                         uint32_t* coef_out, int64_t coef_cap, int64_t* n_coef, int* vop_out, int* n_done);
 
+/* ---------------------------------------------------------------------------
+ * Baseline JPEG split decode — Motion-JPEG AVI frames and the reference's frame<N>.jpg
+ * directories (utils.py:851-860): the host entropy-decodes, the device reconstructs, and the
+ * frames land in device memory bit-identical to libjpeg-turbo's decode (islow IDCT, fancy
+ * upsampling, jdcolor's fixed-point YCbCr -> RGB), stored BGR.
+ *
+ * Supported: SOF0, 8-bit, Huffman coded, one interleaved scan of 1 component (grayscale, 1x1) or
+ * of 3 components YCbCr with luma sampling 1x1, 2x1 or 2x2 over 1x1 chroma; 8-bit DQT; DHT, or
+ * the Annex K tables in every slot 0 / 1 a frame leaves undefined; DRI / RSTn; 0xFF00 stuffing,
+ * fill bytes; APPn / COM skipped; bytes after EOI ignored.  Anything else is reported in
+ * mvp_jpeg_frame_info.status (MVP_JPEG_*), never guessed:
+ *   PROCESS     not baseline sequential Huffman (SOF1, SOF2, arithmetic coding, DNL ...)
+ *   PRECISION   12-bit samples or a 16-bit quantisation table
+ *   COMPONENTS  a component count other than 1 or 3
+ *   SAMPLING    other sampling factors
+ *   SCANS       more than one scan, or a scan that does not interleave all components
+ *   COLOUR      an Adobe APP14 segment, or component ids 'R' 'G' 'B' without JFIF: libjpeg may
+ *               pick a colour transform other than YCbCr
+ *   RANGE       a dequantised coefficient value * q outside int16, where libjpeg-turbo's SIMD
+ *               and C paths differ (no 8-bit encoder writes such a frame)
+ * A malformed or truncated stream is MVP_ERR_ARG with the position in mvp_last_error(); no call
+ * reads past data + bytes.
+ *
+ * mvp_jpeg_info  : the frame's size, components, luma sampling and status from its headers.
+ *                  check_range != 0 also walks the scan, which RANGE, a second scan and a
+ *                  truncated scan need; without it those are left to mvp_jpeg_parse.
+ * mvp_jpeg_parse : one frame.  A supported frame (info->status == MVP_JPEG_OK) writes
+ *                    qt_out[3][64]  the components' quantisation tables, natural (row-major) order;
+ *                    off_out[blocks + 1]  (off_cap entries > blocks): block b owns the entries
+ *                      [off[b], off[b + 1]) of coef_out.  Blocks are numbered in scan order over the
+ *                      MCU-padded component planes: MCU by MCU in raster order (an MCU is
+ *                      8 h_samp x 8 v_samp pixels); inside an MCU the h_samp x v_samp luma blocks in
+ *                      raster order, then the Cb block, then the Cr block.  info->blocks counts them;
+ *                    coef_out  the non-zero QUANTISED coefficients as uint32 entries (natural-order
+ *                      position << 16 | uint16 value), *n_coef of them; coef_cap must be at least
+ *                      min(64 blocks, 4 bytes + blocks) + 64 (an entry takes two bits of the scan).
+ *                      Dequantisation is the device's (the products need more than 16 bits).
+ *                  An unsupported frame writes only *info and *n_coef = 0 and returns MVP_OK.
+ * mvp_jpeg_parse_many : mvp_jpeg_parse over frames data[0..n) in one call (one GIL release from
+ *                  Python): frame k's info[k], qt_out + 192 k, off_out + k off_stride (off_stride
+ *                  entries, > the frames' blocks), its entries packed after frame k-1's in coef_out
+ *                  (n_coef[k]; its offsets count from its own first entry).  Stops before a frame
+ *                  that might not fit (fewer entries left than mvp_jpeg_parse asks for); *n_done =
+ *                  frames handled.  A malformed frame returns its error with *n_done = its index.
+ * mvp_jpeg_reconstruct : stream-ordered; jobs_dev = n_jobs device records of 48 bytes
+ *                  {const uint32 off*, const uint32 coef*, const uint16 qt*, uint8 planes*,
+ *                   uint8 bgr*, uint8 components, h_samp, v_samp, pad[5]}, all device pointers: one
+ *                  frame's offsets, entries and tables as mvp_jpeg_parse wrote them, scratch for its
+ *                  padded component planes (*plane_bytes of mvp_jpeg_scratch; 8-byte aligned) and
+ *                  the [height][width][3] BGR frame out.  All frames are width x height; their
+ *                  sampling may differ.  Two launches: blocks -> planes (dequantise, IDCT), planes
+ *                  -> BGR (upsample, colour).
+ * mvp_jpeg_scratch : the most blocks and plane bytes a width x height frame of any supported
+ *                  sampling has (what to size off_stride - 1 and the scratch with).
+ * ------------------------------------------------------------------------- */
+#define MVP_JPEG_OK 0
+#define MVP_JPEG_PROCESS 1
+#define MVP_JPEG_PRECISION 2
+#define MVP_JPEG_COMPONENTS 3
+#define MVP_JPEG_SAMPLING 4
+#define MVP_JPEG_SCANS 5
+#define MVP_JPEG_COLOUR 6
+#define MVP_JPEG_RANGE 7
+
+typedef struct mvp_jpeg_frame_info {
+    int32_t width, height;
+    int32_t components;      /* 1 or 3 when supported */
+    int32_t h_samp, v_samp;  /* luma sampling factors */
+    int32_t status;          /* MVP_JPEG_OK or the reason the frame is unsupported */
+    int32_t blocks;          /* 8x8 blocks of the scan (supported frames) */
+    int32_t reserved;
+} mvp_jpeg_frame_info;
+
+int mvp_jpeg_info(const uint8_t* data, size_t bytes, int check_range, mvp_jpeg_frame_info* info);
+int mvp_jpeg_parse(const uint8_t* data, size_t bytes, mvp_jpeg_frame_info* info, uint16_t* qt_out, uint32_t* off_out,
+                   int64_t off_cap, uint32_t* coef_out, int64_t coef_cap, int64_t* n_coef);
+int mvp_jpeg_parse_many(int n, const uint8_t* const* data, const size_t* bytes, mvp_jpeg_frame_info* info,
+                        uint16_t* qt_out, uint32_t* off_out, int64_t off_stride, uint32_t* coef_out, int64_t coef_cap,
+                        int64_t* n_coef, int* n_done);
+int mvp_jpeg_scratch(int width, int height, int* blocks, int64_t* plane_bytes);
+int mvp_jpeg_reconstruct(const void* jobs_dev, int n_jobs, int width, int height, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,8 +179,8 @@ def get_pose_2D(frames, model, confidence=0.5, pose_keypoints=range(17), max_pea
 
 
 def video_device():
-    """Where load_frames reconstructs MPEG-4 Part 2 recordings: the GPU (split decode, frames land
-    in HBM) unless MVPOSE_VIDEO_DECODE=host or no GPU is visible."""
+    """Where load_frames reconstructs MPEG-4 Part 2 and JPEG (MJPEG AVI, frame<N>.jpg) recordings:
+    the GPU (split decode, frames land in HBM) unless MVPOSE_VIDEO_DECODE=host or no GPU is visible."""
     if os.environ.get("MVPOSE_VIDEO_DECODE", "device") == "host" or not torch.cuda.is_available():
         return None
     return torch.device("cuda", torch.cuda.current_device())
@@ -191,9 +191,11 @@ def load_frames(recording_paths, start_end_frames=(0, -1), device=None):
     frame_generator :849-900).  A recording is a .npy stack (memory-mapped), an MPEG-4 Part 2
     ('mp4v') MP4 / AVI / raw stream, an MJPEG or uncompressed AVI, a directory of frame<N>.jpg
     files (mvpose.video), or an in-memory array / tensor; other codecs raise
-    NotImplementedError (no decoder in this image).  device: mp4v recordings are then
-    split-decoded onto it (host entropy decoding, GPU reconstruction) and come back as device
-    tensors, bit-identical to the host decoder's frames."""
+    NotImplementedError (no decoder in this image).  device: mp4v recordings, MJPEG AVIs and
+    frame<N>.jpg directories are then split-decoded onto it (host entropy decoding, GPU
+    reconstruction) and come back as device tensors, bit-identical to the host decoders' frames;
+    a JPEG slice larger than half of the device's free memory stays a host array
+    (video.read_recording's max_device_bytes)."""
     from . import video
     if isinstance(recording_paths, (list, tuple)):
         recording_paths = dict(enumerate(recording_paths))

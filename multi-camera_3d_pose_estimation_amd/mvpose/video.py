@@ -18,7 +18,10 @@ rocDecode), so the containers whose codecs ARE available are read here:
 
 Every reader returns (T, H, W, 3) uint8 frames in the channel order cv2 returns them
 (BGR), so the rest of the pipeline applies the reference's cvtColor(RGB2BGR) swap exactly
-as for decoded video.  H.264 / HEVC (QuickTime's usual .mov codecs, record_from_webcams_
+as for decoded video.  With device= the mp4v and the JPEG formats (Motion-JPEG AVIs, frame<N>.jpg
+directories) are split-decoded instead: entropy decoding here on the host, reconstruction on the
+GPU (csrc/mp4v_recon.hip, csrc/jpeg_recon.hip), the same frames bit for bit as a tensor on that
+device.  H.264 / HEVC (QuickTime's usual .mov codecs, record_from_webcams_
 with_quicktime.py:39) raise NotImplementedError: this image has no decoder for them.  Decoded
 pixels are libjpeg's for MJPEG (islow IDCT, fancy upsampling), which is what cv2.imread uses;
 cv2's VideoCapture decodes MJPEG and MPEG-4 with FFmpeg, which is absent here, so parity of
@@ -130,9 +133,21 @@ def _mp4v(config, samples, start, end, device):
     return decode_mp4v_device(config, samples, start, end, device=device)
 
 
-def read_avi(path, start=0, end=None, threads=None, device=None):
-    """Frames [start:end) of an MJPEG / uncompressed AVI -> (T, H, W, 3) uint8 BGR (mp4v streams
-    with device set: a tensor on that device, reconstructed there)."""
+def _fits_device(n_bytes, device, max_device_bytes):
+    """The JPEG readers' memory guard: do n_bytes of decoded frames fit the budget on `device`
+    (max_device_bytes, default half of the memory free there now)?"""
+    if max_device_bytes is None:
+        import torch
+        max_device_bytes = torch.cuda.mem_get_info(torch.device(device))[0] // 2
+    return n_bytes <= max_device_bytes
+
+
+def read_avi(path, start=0, end=None, threads=None, device=None, max_device_bytes=None):
+    """Frames [start:end) of an MJPEG / uncompressed AVI -> (T, H, W, 3) uint8 BGR.  With device set,
+    mp4v and MJPEG streams come back as a tensor on that device, reconstructed there
+    (decode_mp4v_device / decode_jpeg_device; bit-identical frames) — MJPEG only while the slice's
+    T * H * W * 3 bytes are at most max_device_bytes (default: half of the device's free memory),
+    else as the host array."""
     with open(path, "rb") as f:
         buf = mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
         try:
@@ -153,6 +168,10 @@ def read_avi(path, start=0, end=None, threads=None, device=None):
                 return _mp4v(info.strf_extra, (bytes(buf[d:d + n]) for d, n in info.chunks), start, end, device)
             elif info.codec == "mjpeg":
                 datas = [bytes(buf[d:d + n]) for d, n in chunks]
+                if device is not None and _fits_device(out.nbytes, device, max_device_bytes):
+                    return _decode_jpeg_device(
+                        datas, (H, W), device, threads=threads,
+                        mismatch=lambda i, shape: f"{path}: frame {i} is {shape}, stream header says {(H, W, 3)}")
                 workers = max(1, min(int(threads or os.cpu_count() or 1), 16))
 
                 def dec(i):
@@ -171,9 +190,12 @@ def read_avi(path, start=0, end=None, threads=None, device=None):
             buf.close()
 
 
-def read_image_dir(path, start=0, end=None, threads=None) -> np.ndarray:
+def read_image_dir(path, start=0, end=None, threads=None, device=None, max_device_bytes=None):
     """The reference's process_image_files (utils.py:851-860): *.jpg files of `path`
-    ordered by the integer after "frame", sliced [start:end) -> (T, H, W, 3) uint8 BGR."""
+    ordered by the integer after "frame", sliced [start:end) -> (T, H, W, 3) uint8 BGR.  With
+    device set the frames are split-decoded onto it (decode_jpeg_device) and come back as a tensor
+    there, bit-identical — while their T * H * W * 3 bytes are at most max_device_bytes (default:
+    half of the device's free memory), else as the host array."""
     names = [f for f in os.listdir(path) if f.endswith("jpg")]
     names.sort(key=lambda x: int(x.split("frame")[1].split(".")[0]))
     names = names[slice(start, end)]
@@ -181,9 +203,20 @@ def read_image_dir(path, start=0, end=None, threads=None) -> np.ndarray:
         return np.empty((0, 0, 0, 3), np.uint8)
     workers = max(1, min(int(threads or os.cpu_count() or 1), 16))
 
-    def load(n):
+    def read(n):
         with open(os.path.join(path, n), "rb") as f:
-            return _decode_jpeg(f.read())
+            return f.read()
+
+    if device is not None:
+        datas = [read(n) for n in names]
+        H, W = _jpeg_size(datas[0])
+        if _fits_device(len(datas) * H * W * 3, device, max_device_bytes):
+            return _decode_jpeg_device(datas, (H, W), device, threads=threads,
+                                       mismatch=lambda i, shape: f"{path}: frames of different sizes")
+        del datas
+
+    def load(n):
+        return _decode_jpeg(read(n))
 
     with ThreadPoolExecutor(workers) as pool:
         frames = list(pool.map(load, names))
@@ -192,15 +225,18 @@ def read_image_dir(path, start=0, end=None, threads=None) -> np.ndarray:
     return np.stack(frames)
 
 
-def read_recording(path, start=0, end=-1, device=None):
+def read_recording(path, start=0, end=-1, device=None, max_device_bytes=None):
     """One camera's recording, sliced [start:end] with Python semantics (the reference's
     default [0, -1] drops the last frame) -> (T, H, W, 3) uint8 BGR (memory-mapped for .npy).
-    device: MPEG-4 Part 2 recordings are then split-decoded — entropy decoding on the host,
-    reconstruction on the GPU (decode_mp4v_device) — and come back as a tensor on that device
-    (bit-identical frames); other formats still return host arrays."""
+    device: MPEG-4 Part 2 recordings, Motion-JPEG AVIs and frame<N>.jpg directories are then
+    split-decoded — entropy decoding on the host, reconstruction on the GPU (decode_mp4v_device,
+    decode_jpeg_device) — and come back as a tensor on that device (bit-identical frames);
+    uncompressed AVIs and .npy stacks still return host arrays.  max_device_bytes: the JPEG
+    formats return the host array instead when the slice's T * H * W * 3 bytes exceed it (default:
+    half of the device's free memory)."""
     p = str(path)
     if os.path.isdir(p):
-        return read_image_dir(p, start, end)
+        return read_image_dir(p, start, end, device=device, max_device_bytes=max_device_bytes)
     low = p.lower()
     if low.endswith(".npy"):
         arr = np.load(p, mmap_mode="r")
@@ -212,7 +248,7 @@ def read_recording(path, start=0, end=-1, device=None):
     with open(p, "rb") as f:
         head = f.read(12)
     if head[0:4] == b"RIFF" and head[8:12] == b"AVI ":
-        return read_avi(p, start, end, device=device)
+        return read_avi(p, start, end, device=device, max_device_bytes=max_device_bytes)
     if head[4:8] in (b"ftyp", b"moov", b"mdat", b"free", b"wide", b"skip"):
         return read_mp4(p, start, end, device=device)
     if head[0:3] == b"\0\0\1" and (head[3] in (0xB0, 0xB3, 0xB5, 0xB6) or head[3] <= 0x2F):
@@ -220,6 +256,214 @@ def read_recording(path, start=0, end=-1, device=None):
     raise NotImplementedError(
         f"{p}: no decoder for this container/codec in this image (MPEG-4 Part 2 in MP4/MOV/AVI/raw, MJPEG and "
         "uncompressed AVI, frame*.jpg directories and .npy stacks are supported)")
+
+
+# ------------------------------------------------------------------ baseline JPEG, split decode
+JPEG_INFO_DTYPE = np.dtype([("width", "<i4"), ("height", "<i4"), ("components", "<i4"), ("h_samp", "<i4"),
+                            ("v_samp", "<i4"), ("status", "<i4"), ("blocks", "<i4"), ("reserved", "<i4")])
+JPEG_JOB_DTYPE = np.dtype([("off", "<u8"), ("coef", "<u8"), ("qt", "<u8"), ("planes", "<u8"), ("bgr", "<u8"),
+                           ("ncomp", "u1"), ("hs", "u1"), ("vs", "u1"), ("pad0", "u1"), ("pad1", "<u4")])  # jpeg.h Job
+JPEG_UNSUPPORTED = {1: "process", 2: "precision", 3: "components", 4: "sampling", 5: "scans", 6: "colour", 7: "range"}
+JPEG_LAUNCH_FRAMES = 32   # frames per mvp_jpeg_reconstruct launch: they share one set of scratch planes
+
+
+def jpeg_info(data: bytes, check_range: bool = False):
+    """mvp_jpeg_info of one frame -> a JPEG_INFO_DTYPE record (status 0: the split decode takes
+    it, else JPEG_UNSUPPORTED's reason); raises MvposeError on a malformed / truncated stream.
+    check_range: also walk the scan (the int16 range condition, a second scan, a truncated scan)."""
+    from . import _lib
+    info = np.zeros(1, JPEG_INFO_DTYPE)
+    buf = np.frombuffer(data, np.uint8)
+    _lib.call("mvp_jpeg_info", buf.ctypes.data, buf.size, int(bool(check_range)), info.ctypes.data)
+    return info[0]
+
+
+def _jpeg_entry_bound(blocks, n_bytes):
+    """Entries a frame can hold (include/mvpose.h, mvp_jpeg_parse): an entry takes two bits of
+    the scan but for one a block, and 64 fill a block."""
+    return min(64 * blocks, 4 * n_bytes + blocks) + 64
+
+
+def parse_jpeg(data: bytes):
+    """mvp_jpeg_parse of one frame -> (info, qt (3, 64) uint16, off (blocks + 1) uint32, coef
+    uint32 entries); qt / off / coef are None when info['status'] says the frame is unsupported."""
+    import ctypes
+    from . import _lib
+    info = jpeg_info(data)
+    if info["status"]:
+        return info, None, None, None
+    buf = np.frombuffer(data, np.uint8)
+    blocks = int(info["blocks"])
+    out = np.zeros(1, JPEG_INFO_DTYPE)
+    qt = np.zeros((3, 64), np.uint16)
+    off = np.zeros(blocks + 1, np.uint32)
+    coef = np.empty(_jpeg_entry_bound(blocks, buf.size), np.uint32)
+    n = ctypes.c_int64()
+    _lib.call("mvp_jpeg_parse", buf.ctypes.data, buf.size, out.ctypes.data, qt.ctypes.data, off.ctypes.data, off.size,
+              coef.ctypes.data, coef.size, ctypes.byref(n))
+    if out[0]["status"]:
+        return out[0], None, None, None
+    return out[0], qt, off, coef[:n.value].copy()
+
+
+def _jpeg_size(data: bytes):
+    """(H, W) of a frame: from its headers, or (a stream the parser rejects) from PIL's decode."""
+    from . import _lib
+    try:
+        info = jpeg_info(data)
+        return int(info["height"]), int(info["width"])
+    except _lib.MvposeError:
+        return _decode_jpeg(data).shape[:2]
+
+
+def decode_jpeg_device(datas, device="cuda", stream=None, threads=None, timings: dict | None = None, size=None):
+    """JPEG frames (Motion-JPEG samples, frame<N>.jpg files) decoded onto the GPU: a (n, H, W, 3)
+    uint8 BGR tensor on `device`, bit-identical to the host reader's frames (libjpeg through PIL).
+
+    Every frame is probed (mvp_jpeg_info); the baseline frames are entropy-decoded on a host
+    thread pool of at most 16 workers (mvp_jpeg_parse_many: per-block offsets + the non-zero
+    quantised coefficients) into pinned buffers and copied to the device on a copy stream while
+    other frames still parse; mvp_jpeg_reconstruct then dequantises, runs libjpeg's islow IDCT,
+    fancy upsampling and YCbCr -> RGB there.  Frames the split decode does not take (progressive,
+    CMYK, ... — JPEG_UNSUPPORTED) and frames the parser rejects are decoded one by one by PIL and
+    copied into their slots, so a truncated frame raises what PIL raises.  size: the (H, W) every
+    frame must have (default: the first frame's), else ValueError.  stream: the stream the work is
+    queued on (default: the device's current one); that current stream waits for it before this
+    returns.  timings: filled with the host phases' seconds (parse, pack, launch; the launches are
+    asynchronous) and the number of frames that fell back."""
+    datas = [x if isinstance(x, bytes) else bytes(x) for x in datas]
+    if size is None:
+        size = _jpeg_size(datas[0]) if datas else (0, 0)
+    H, W = size
+    return _decode_jpeg_device(datas, (int(H), int(W)), device, stream=stream, threads=threads, timings=timings,
+                               mismatch=lambda i, shape: f"frame {i} is {shape}, stream header says {(H, W, 3)}")
+
+
+def _decode_jpeg_device(datas, size, device, mismatch, stream=None, threads=None, timings=None):
+    import ctypes
+    import time
+    import torch
+    from . import _lib
+    H, W = size
+    n = len(datas)
+    dev = torch.device(device)
+    caller = torch.cuda.current_stream(dev)
+    s = stream if stream is not None else caller
+    # as in decode_mp4v_device: `out` is written by launches on `s`, so it is allocated there, and
+    # the caller's stream waits for `s` before this returns
+    with torch.cuda.stream(s):
+        out = torch.empty((n, H, W, 3), dtype=torch.uint8, device=dev)
+    if n == 0 or H == 0 or W == 0:
+        return out
+    t_parse = time.perf_counter()
+    infos = np.zeros(n, JPEG_INFO_DTYPE)
+    split = np.zeros(n, bool)                              # frames the split decode takes
+    for i, data in enumerate(datas):
+        buf = np.frombuffer(data, np.uint8)
+        if buf.size and _lib.lib.mvp_jpeg_info(buf.ctypes.data, buf.size, 0, infos[i:].ctypes.data) == 0:
+            split[i] = infos[i]["status"] == 0
+            if split[i] and (infos[i]["height"], infos[i]["width"]) != (H, W):
+                raise ValueError(mismatch(i, (int(infos[i]["height"]), int(infos[i]["width"]), 3)))
+    blocks, plane_bytes = ctypes.c_int(), ctypes.c_int64()
+    _lib.call("mvp_jpeg_scratch", W, H, ctypes.byref(blocks), ctypes.byref(plane_bytes))
+    stride = blocks.value + 1                              # offsets of one frame
+    head_bytes = stride * 4 + 384                          # + its three quantisation tables
+    todo = np.flatnonzero(split)
+    workers = max(1, min(int(threads or os.cpu_count() or 1), 16))
+    per = max(1, min(16, -(-len(todo) // (2 * workers))))
+    chunks = [todo[k:k + per] for k in range(0, len(todo), per)]
+    copy_stream = torch.cuda.Stream(dev)
+
+    def parse(ci):
+        """One chunk of frames in native calls (the GIL is released for each), then its two H2D
+        copies -> (frames parsed, their heads on the device, their entries on the device, entry
+        counts, the frames of the chunk left to PIL)."""
+        idx = chunks[ci]
+        m = len(idx)
+        ptrs = (ctypes.c_char_p * m)(*[datas[i] for i in idx])
+        sizes = np.array([len(datas[i]) for i in idx], np.uint64)
+        cap = int(sum(_jpeg_entry_bound(int(infos[i]["blocks"]), len(datas[i])) for i in idx))
+        coef = np.empty(cap, np.uint32)
+        head_h = torch.empty(m * head_bytes, dtype=torch.uint8, pin_memory=True)
+        head_np = head_h.numpy()
+        off_np, qt_np = head_np[:m * stride * 4], head_np[m * stride * 4:]
+        info = np.zeros(m, JPEG_INFO_DTYPE)
+        ncoef = np.zeros(m, np.int64)
+        good = np.zeros(m, bool)
+        k, used = 0, 0
+        while k < m:
+            done = ctypes.c_int()
+            rc = _lib.lib.mvp_jpeg_parse_many(
+                m - k, ctypes.addressof(ptrs) + 8 * k, sizes.ctypes.data + 8 * k, info.ctypes.data + 32 * k,
+                qt_np.ctypes.data + 384 * k, off_np.ctypes.data + 4 * stride * k, stride, coef.ctypes.data + 4 * used,
+                cap - used, ncoef.ctypes.data + 8 * k, ctypes.byref(done))
+            d = done.value
+            good[k:k + d] = info["status"][k:k + d] == 0
+            used += int(ncoef[k:k + d].sum())
+            k += d
+            if rc != 0:                                    # frame k is malformed: PIL's to report
+                ncoef[k] = 0
+                k += 1
+            elif d == 0:
+                raise _lib.MvposeError("mvp_jpeg_parse_many", rc, "no frame fitted the coefficient buffer")
+        coef_h = torch.empty(max(1, used), dtype=torch.int32, pin_memory=True)
+        coef_h.numpy()[:used] = coef[:used].view(np.int32)
+        with torch.cuda.stream(copy_stream):
+            head_d = head_h.to(dev, non_blocking=True)
+            coef_d = coef_h.to(dev, non_blocking=True)
+        head_d.record_stream(s)                            # read by the reconstruction launches
+        coef_d.record_stream(s)
+        return idx, head_d, coef_d, ncoef, good, info, (head_h, coef_h)
+
+    if workers == 1 or len(chunks) <= 1:
+        parsed = [parse(c) for c in range(len(chunks))]
+    else:
+        with ThreadPoolExecutor(min(workers, len(chunks))) as pool:
+            parsed = list(pool.map(parse, range(len(chunks))))
+    t_pack = time.perf_counter()
+    jobs = []
+    for idx, head_d, coef_d, ncoef, good, info, _ in parsed:
+        m = len(idx)
+        first = np.cumsum(ncoef) - ncoef
+        for k in np.flatnonzero(good):
+            jobs.append((int(idx[k]), head_d.data_ptr() + 4 * stride * int(k), coef_d.data_ptr() + 4 * int(first[k]),
+                         head_d.data_ptr() + 4 * stride * m + 384 * int(k), int(info[k]["components"]),
+                         int(info[k]["h_samp"]), int(info[k]["v_samp"])))
+            split[idx[k]] = True
+        split[idx[~good]] = False
+    t_launch = time.perf_counter()
+    with torch.cuda.stream(s):
+        if jobs:
+            slot = (plane_bytes.value + 63) & ~63
+            planes = torch.empty(min(len(jobs), JPEG_LAUNCH_FRAMES) * slot, dtype=torch.uint8, device=dev)
+            jl = np.zeros(len(jobs), JPEG_JOB_DTYPE)
+            frame = np.array([j[0] for j in jobs], np.int64)
+            jl["off"] = [j[1] for j in jobs]
+            jl["coef"] = [j[2] for j in jobs]
+            jl["qt"] = [j[3] for j in jobs]
+            jl["planes"] = planes.data_ptr() + (np.arange(len(jobs)) % JPEG_LAUNCH_FRAMES) * slot
+            jl["bgr"] = out.data_ptr() + frame * (H * W * 3)
+            jl["ncomp"], jl["hs"], jl["vs"] = ([j[k] for j in jobs] for k in (4, 5, 6))
+            jobs_d = torch.from_numpy(jl.view(np.uint8).copy()).pin_memory().to(dev, non_blocking=True)
+            s.wait_stream(copy_stream)
+            for a in range(0, len(jobs), JPEG_LAUNCH_FRAMES):
+                _lib.call("mvp_jpeg_reconstruct", jobs_d.data_ptr() + a * JPEG_JOB_DTYPE.itemsize,
+                          min(JPEG_LAUNCH_FRAMES, len(jobs) - a), W, H, s.cuda_stream)
+        # the frames left to libjpeg, one by one
+        rest = np.flatnonzero(~split)
+        for i in rest:
+            fr = _decode_jpeg(datas[i])
+            if fr.shape != (H, W, 3):
+                raise ValueError(mismatch(int(i), fr.shape))
+            out[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)))
+    if s != caller:
+        caller.wait_stream(s)
+        out.record_stream(caller)                         # allocated on s, read by the caller's stream
+    if timings is not None:
+        t_end = time.perf_counter()
+        timings.update(parse=t_pack - t_parse, pack=t_launch - t_pack, launch=t_end - t_launch,
+                       fallback=int(len(rest)), frames=n, coef_entries=int(sum(int(p[3].sum()) for p in parsed)))
+    return out
 
 
 # ------------------------------------------------------------------ MPEG-4 Part 2 ('mp4v')
